@@ -9,7 +9,13 @@ Single node, one rank per GPU over RCCL:
 Parallelism by N (weak scaling toward the 8-GPU DP2xTP2xPP2 target):
   1 -> single | 2 -> DP2 | 4 -> DP4 | 8 -> DP2xTP2xPP2
 
-Rank 0 prints ONE JSON line with the whole-job tokens/s.
+Rank 0 prints ONE JSON line with the whole-job tokens/s and ms_per_step.
+
+A plain run sets up, warms up, times --steps steps and prints that line;
+--dump-outputs DIR additionally saves the last timed step's loss and seeded
+samples of the fp32 optimizer state (master-weight change, Adam first
+moment) as DIR/*.npy, so two builds can be compared output for output.
+--full is where secondary measurements go (none exist today).
 """
 
 import argparse
@@ -42,7 +48,80 @@ def parse_args():
                    help="hidden+attention dropout (the reference's "
                         "pretrain configs run 0.1; in-kernel Philox "
                         "attention dropout on the flash path)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write DIR/<name>.npy "
+                        "(float32): loss (what the last timed step "
+                        "returned) and fixed seeded samples of the "
+                        "optimizer state the steps left behind: "
+                        "master_delta_sample (fp32 master weights minus "
+                        "their initial values) and exp_avg_sample (Adam's "
+                        "running mean of the gradients)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement; the plain "
+                        "run does only what the headline figure needs. "
+                        "This benchmark has no secondary measurements, so "
+                        "the flag changes nothing today")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
+
+
+# --dump-outputs samples this many elements of every optimizer bucket
+# (99 buckets for GPT-6.7B: 6.5 MB of float32 per file, budget is 64 MB)
+DUMP_PER_BUCKET = 16384
+DUMP_SEED = 20240229
+
+
+class OutputDumper:
+    """Collects what --dump-outputs writes.
+
+    The loss alone says little about the backward pass and the optimizer:
+    the LR schedule is still in its first warmup steps, so the bf16 weights
+    barely move and the loss stays the forward loss of the initial model.
+    The fp32 optimizer state does react, so a fixed, seeded sample of it is
+    written too: the master weights' change since construction and Adam's
+    first moment (an average of the clipped gradients of every step run).
+    Needs the fused optimizer's buckets; other optimizers get loss only.
+    """
+
+    def __init__(self, out_dir, optimizer):
+        self.out_dir = out_dir
+        sd = optimizer.state_dict() if optimizer is not None else {}
+        self.buckets = sd.get("buckets") if isinstance(sd, dict) else None
+        if not self.buckets or "master" not in self.buckets[0]:
+            self.buckets = None
+            print("bench: --dump-outputs: optimizer has no fused buckets, "
+                  "writing loss.npy only", file=sys.stderr)
+            return
+        g = torch.Generator(device="cpu")
+        g.manual_seed(DUMP_SEED)
+        self.idx = []
+        for b in self.buckets:
+            n = b["master"].numel()
+            k = min(n, DUMP_PER_BUCKET)
+            self.idx.append(torch.randint(n, (k,), generator=g)
+                            .to(b["master"].device))
+        self.master0 = self._sample("master")
+
+    def _sample(self, key):
+        return torch.cat([b[key].detach().reshape(-1)[i].float()
+                          for b, i in zip(self.buckets, self.idx)])
+
+    def write(self, loss):
+        import numpy as np
+        os.makedirs(self.out_dir, exist_ok=True)
+
+        def save(name, t):
+            np.save(os.path.join(self.out_dir, name + ".npy"),
+                    t.detach().float().cpu().numpy())
+
+        save("loss", loss.reshape(1))
+        if self.buckets is not None:
+            save("master_delta_sample", self._sample("master") - self.master0)
+            save("exp_avg_sample", self._sample("exp_avg"))
 
 
 MODELS = {
@@ -80,8 +159,8 @@ def main():
     # defaults from the measured 1-GPU sweep (profiles/): micro=16 puts
     # the hipBLASLt GEMMs at M=16384 (same-box A/B vs micro8: 26234 vs
     # 25904 tok/s; micro32 gains nothing more and doubles activation
-    # memory — gpurun_out/r2_m16_ab.txt, r2_m32.txt). Under pipeline
-    # parallel trade GEMM width for more micro-batches
+    # memory — profiles/r02_micro16_ab.txt). Under pipeline parallel
+    # trade GEMM width for more micro-batches
     # (1F1B bubble = (pp-1)/(acc+pp-1)).
     if pp > 1:
         micro = args.micro_batch or 4
@@ -129,6 +208,10 @@ def main():
              torch.randint(0, vocab, (local_bs, seq), device=device),
              torch.ones(local_bs, seq, device=device))
 
+    dumper = None
+    if rank == 0 and args.dump_outputs:
+        dumper = OutputDumper(args.dump_outputs, engine.optimizer)
+
     def barrier_sync():
         if dist.is_initialized():
             dist.barrier()
@@ -155,6 +238,9 @@ def main():
     tokens_per_step = global_batch * seq
     toks_per_s = tokens_per_step * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if dumper is not None and loss is not None:
+        dumper.write(loss)
 
     if rank == 0:
         metric = "tokens/sec/GPU GPT-3-6.7B pretrain, DP2×TP2×PP2 at 1/2/4/8 MI355X"

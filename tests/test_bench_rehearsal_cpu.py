@@ -54,6 +54,71 @@ def test_bench_world8_dp2tp2pp2():
     assert rec["config"]["loss"] is not None
 
 
+def _run_bench_single(steps, *extra):
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps),
+           "--warmup", "1", "--model", "GPT-TEST", "--seq-len", "32",
+           "--micro-batch", "2", "--acc-steps", "2", *extra]
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True,
+                         text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    json_lines = [l for l in out.stdout.splitlines()
+                  if l.startswith("{") and '"metric"' in l]
+    assert len(json_lines) == 1, out.stdout
+    return json.loads(json_lines[0])
+
+
+DUMP_NAMES = ["exp_avg_sample", "loss", "master_delta_sample"]
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes float32 arrays that are reproducible run to
+    run and that react to the training path: a run with --steps 1 instead
+    of --steps 3 (everything else equal) must move the optimizer-state
+    samples by far more than two identical runs differ. --full is accepted
+    and leaves the headline line's fields in place."""
+    import numpy as np
+    dirs = {k: str(tmp_path / k) for k in "abc"}
+    recs = {"a": _run_bench_single(3, "--dump-outputs", dirs["a"]),
+            "b": _run_bench_single(3, "--dump-outputs", dirs["b"], "--full"),
+            "c": _run_bench_single(1, "--dump-outputs", dirs["c"])}
+    for rec in recs.values():
+        assert rec["ms_per_step"] > 0
+        assert rec["unit"] == "tokens/s" and rec["higher_is_better"] is True
+        assert rec["dtype"] == "bf16"
+    out = {}
+    for k, d in dirs.items():
+        assert sorted(os.listdir(d)) == [n + ".npy" for n in DUMP_NAMES]
+        out[k] = {n: np.load(os.path.join(d, n + ".npy")) for n in DUMP_NAMES}
+        for n, arr in out[k].items():
+            assert arr.dtype == np.float32 and arr.ndim == 1, n
+            assert np.isfinite(arr).all(), n
+        assert sum(a.nbytes for a in out[k].values()) < 64 * 2 ** 20
+    assert out["a"]["loss"].shape == (1,)
+    assert float(out["a"]["loss"][0]) == pytest.approx(
+        recs["a"]["config"]["loss"], rel=1e-6)
+
+    def rel(x, y):  # size of the difference relative to size of the output
+        x, y = x.astype(np.float64), y.astype(np.float64)
+        return np.linalg.norm(x - y) / np.linalg.norm(x)
+
+    for n in DUMP_NAMES:
+        # same arguments: same inputs, same CPU arithmetic
+        assert rel(out["a"][n], out["b"][n]) <= 1e-6, n
+    for n in ("master_delta_sample", "exp_avg_sample"):
+        assert out["a"][n].shape == out["c"][n].shape
+        assert np.linalg.norm(out["a"][n]) > 0, n
+        # 4 optimizer steps against 2: under the linear LR warmup the
+        # master weights have moved by about (1+2+3+4)/(1+2) as much, and
+        # the first moment has averaged two more gradients
+        assert rel(out["a"][n], out["c"][n]) > 0.2, n
+    # the weights moved further with more timed steps
+    assert np.linalg.norm(out["a"]["master_delta_sample"]) > \
+        1.5 * np.linalg.norm(out["c"]["master_delta_sample"])
+
+
 def test_bench_defaults_contract():
     """Driver-contract guard: model table, topology mapping and the
     measured micro/acc defaults must not drift."""
