@@ -31,6 +31,9 @@ def main():
     p.add_argument("--gen-len", type=int, default=64)
     p.add_argument("--batches", type=str, default="1,2,4,8,16")
     p.add_argument("--top-p", type=float, default=0.9)
+    p.add_argument("--static-cache", action="store_true",
+                   help="preallocated KV cache + fused decode attention "
+                        "(Generation.static_kv_cache)")
     args = p.parse_args()
 
     from paddlefleetx_amd.parallel.env import set_hcg
@@ -56,11 +59,13 @@ def main():
             "top_p": args.top_p,
             "use_topp_sampling": True,
             "eos_token_id": vocab - 1,
+            "static_kv_cache": args.static_cache,
         })
     model.eval()
 
     print(f"# decode bench {args.model} prompt={args.prompt_len} "
-          f"gen={args.gen_len} top_p={args.top_p} ({dev})")
+          f"gen={args.gen_len} top_p={args.top_p} "
+          f"static_cache={args.static_cache} ({dev})")
     for bs in [int(b) for b in args.batches.split(",")]:
         ids = torch.randint(0, vocab - 2, (bs, args.prompt_len), device=dev)
         with torch.no_grad():

@@ -68,6 +68,10 @@ torch::Tensor attn_bwd_packed(torch::Tensor dout, torch::Tensor qkv,
                               torch::Tensor o, torch::Tensor lse,
                               long num_heads, double scale, double p_drop,
                               long seed);
+// decode_attention.hip
+torch::Tensor decode_attn(torch::Tensor qkv, torch::Tensor k_cache,
+                          torch::Tensor v_cache, torch::Tensor seq_lens,
+                          double scale, long max_seq_len, long num_splits);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -123,6 +127,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"),
         py::arg("num_heads"), py::arg("scale"),
         py::arg("p_drop") = 0.0, py::arg("seed") = 0);
+  m.def("decode_attn", &decode_attn,
+        "single-token attention over a preallocated KV cache (in-place "
+        "append, split-KV)",
+        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("seq_lens"), py::arg("scale"), py::arg("max_seq_len"),
+        py::arg("num_splits") = 0);
   m.def("topp_select", &topp_select, "top-p nucleus cutoff + draw");
   m.def("mfma_gemm16_probe", &mfma_gemm16_probe,
         "debug: 16x16x32 MFMA fragment-layout probe");

@@ -6,7 +6,9 @@ Reference: ppfleetx/models/language_model/gpt/dygraph/single_model.py
 and the hybrid twin hybrid_model.py:1209.
 
 MI355X-native notes: the decode loop runs the same GPTModel with per-layer
-KV caches ([B, H, S, D] tensors grown by concat); sampling post-processing
+KV caches ([B, H, S, D] tensors grown by concat, or with `static_kv_cache`
+one preallocated StaticKVCache appended in place by the fused decode
+attention kernel, csrc/decode_attention.hip); sampling post-processing
 uses the hand-written gfx950 top-p kernel (csrc/topp.hip) when
 `use_topp_sampling` is on, replacing the reference's CUB-based
 ppfleetx/ops/topp_sampling.cu.
@@ -20,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from paddlefleetx_amd.models.gpt.model import GPTModel
+from paddlefleetx_amd.models.gpt.model import GPTModel, StaticKVCache
 from paddlefleetx_amd.models.gpt.processor import get_logits_processor
 from paddlefleetx_amd.ops import topp_sampling
 from paddlefleetx_amd.parallel.tp import parallel_matmul
@@ -70,6 +72,7 @@ class GPTForGeneration(nn.Module):
         self.eos_token_id = int(cfg.get("eos_token_id", 50256))
         self.pad_token_id = int(cfg.get("pad_token_id", 0))
         self.num_return_sequences = int(cfg.get("num_return_sequences", 1))
+        self.static_kv_cache = bool(cfg.get("static_kv_cache", False))
 
     # -- one forward --------------------------------------------------------
     def _logits(self, input_ids, position_ids, caches):
@@ -79,6 +82,13 @@ class GPTForGeneration(nn.Module):
             hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight,
             parallel_output=False)
         return logits.float(), new_caches
+
+    def _new_static_cache(self, batch_size: int, max_len: int, device
+                          ) -> StaticKVCache:
+        attn = self.gpt.layers[0].attn
+        return StaticKVCache(len(self.gpt.layers), batch_size,
+                             attn.num_heads_local, max_len, attn.head_dim,
+                             dtype=attn.qkv.weight.dtype, device=device)
 
     def sample(self, input_ids: torch.Tensor,
                logits_processors=None) -> torch.Tensor:
@@ -94,7 +104,12 @@ class GPTForGeneration(nn.Module):
         position_ids = torch.arange(prompt_len, device=device).unsqueeze(0) \
             .expand(B, -1)
         # prefill: full prompt builds the KV cache (single_model.py:1285)
-        logits, caches = self._logits(input_ids, position_ids, None)
+        caches = None
+        if self.static_kv_cache:
+            # one fixed-address cache per call, filled in place
+            caches = self._new_static_cache(
+                B, prompt_len + self.max_length, device)
+        logits, caches = self._logits(input_ids, position_ids, caches)
 
         unfinished = torch.ones(B, dtype=torch.bool, device=device)
         all_ids = input_ids

@@ -22,7 +22,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.utils.checkpoint import checkpoint
 
-from paddlefleetx_amd.ops import (FusedLayerNorm, bias_gelu, flash_attention,
+from paddlefleetx_amd.ops import (FusedLayerNorm, bias_gelu,
+                                  decode_attention, flash_attention,
                                   flash_attention_packed,
                                   fused_softmax_causal)
 from paddlefleetx_amd.parallel.env import get_hcg
@@ -41,6 +42,52 @@ __all__ = [
 ]
 
 KVCache = Tuple[torch.Tensor, torch.Tensor]  # ([B,H,S,D] k, [B,H,S,D] v)
+
+
+class StaticKVSlot:
+    """One layer's view of a StaticKVCache: its k/v buffers plus the
+    shared lengths. Layers read `lens`/`max_len`, never write them."""
+
+    __slots__ = ("owner", "k", "v")
+
+    def __init__(self, owner: "StaticKVCache", k: torch.Tensor,
+                 v: torch.Tensor):
+        self.owner, self.k, self.v = owner, k, v
+
+
+class StaticKVCache:
+    """Preallocated, fixed-address KV cache appended to in place.
+
+    Per-layer k/v buffers [B, h_local, Smax, D] (torch.empty: positions
+    past the current length are uninitialised and never read), ONE shared
+    device int32 lens[B] and a host-side max_len counter. Indexing gives
+    layer i its slot; GPTModel.forward calls advance() once per forward,
+    after the layer loop, so every layer of a step sees the same lengths.
+    """
+
+    def __init__(self, num_layers: int, batch_size: int, num_heads: int,
+                 max_len: int, head_dim: int,
+                 dtype: Optional[torch.dtype] = None, device=None):
+        self.capacity = int(max_len)
+        shape = (batch_size, num_heads, self.capacity, head_dim)
+        self.k = [torch.empty(shape, dtype=dtype, device=device)
+                  for _ in range(num_layers)]
+        self.v = [torch.empty(shape, dtype=dtype, device=device)
+                  for _ in range(num_layers)]
+        self.lens = torch.zeros(batch_size, dtype=torch.int32, device=device)
+        self.max_len = 0  # host mirror of max(lens)
+
+    def __len__(self) -> int:
+        return len(self.k)
+
+    def __getitem__(self, i: int) -> StaticKVSlot:
+        return StaticKVSlot(self, self.k[i], self.v[i])
+
+    def advance(self, n: int) -> None:
+        assert self.max_len + n <= self.capacity, \
+            f"StaticKVCache overflow: {self.max_len}+{n} > {self.capacity}"
+        self.lens += n
+        self.max_len += n
 
 
 class MultiHeadAttention(nn.Module):
@@ -92,6 +139,11 @@ class MultiHeadAttention(nn.Module):
                 ) -> Tuple[torch.Tensor, Optional[KVCache]]:
         qkv = self.qkv(x)
         cp = get_hcg().get_context_parallel_world_size()
+        if isinstance(cache, StaticKVSlot):
+            assert not self.sequence_parallel and cp == 1, \
+                "StaticKVCache is not supported on sequence-parallel or " \
+                "context-parallel attention layers"
+            return self._forward_static(qkv, cache)
         if (cp > 1 and cache is None and not use_cache
                 and not self.sequence_parallel):
             # Ulysses CP: x is the [B, S/cp, H] sequence shard; all-to-all
@@ -180,6 +232,39 @@ class MultiHeadAttention(nn.Module):
             o = o.transpose(1, 2).reshape(B, S, -1)  # [B, S, H/mp]
         out = self.out_proj(o)
         return out, new_cache
+
+    def _forward_static(self, qkv: torch.Tensor, slot: StaticKVSlot
+                        ) -> Tuple[torch.Tensor, StaticKVSlot]:
+        """Inference against a preallocated cache slot. Decode (S == 1) is
+        ONE fused kernel on the packed QKV view (in-place append + split-KV
+        attention); prefill computes attention as the no-cache forward does
+        and copies K/V into the slot."""
+        assert not (self.training and self.attn_dropout_p > 0.0), \
+            "StaticKVCache is inference-only (attention dropout is on)"
+        B, S, _ = qkv.shape
+        packed = qkv.view(B, S, self.num_heads_local, 3, self.head_dim)
+        n_cached = slot.owner.max_len
+        assert n_cached + S <= slot.owner.capacity, \
+            f"StaticKVCache overflow: {n_cached}+{S} > {slot.owner.capacity}"
+        if S == 1:
+            o = decode_attention(packed, slot.k, slot.v, slot.owner.lens,
+                                 scale=self.scale, max_seq_len=n_cached + 1)
+            return self.out_proj(o), slot
+        assert n_cached == 0, \
+            "StaticKVCache prefill (S > 1) needs an empty cache"
+        slot.k[:, :, :S].copy_(packed[:, :, :, 1].transpose(1, 2))
+        slot.v[:, :, :S].copy_(packed[:, :, :, 2].transpose(1, 2))
+        if self.fused_attn:
+            o = flash_attention_packed(packed, self.num_heads_local,
+                                       scale=self.scale)
+        else:
+            q = packed[:, :, :, 0].transpose(1, 2)  # [B, h, S, D]
+            k = packed[:, :, :, 1].transpose(1, 2)
+            v = packed[:, :, :, 2].transpose(1, 2)
+            scores = torch.matmul(q, k.transpose(-1, -2))
+            probs = fused_softmax_causal(scores, self.scale)
+            o = torch.matmul(probs, v).transpose(1, 2).reshape(B, S, -1)
+        return self.out_proj(o), slot
 
 
 class FFN(nn.Module):
@@ -404,6 +489,10 @@ class GPTModel(nn.Module):
                 new_caches.append(c)
             else:
                 x = layer(x, cache=cache_i)
+        if isinstance(caches, StaticKVCache):
+            # every layer appended at the same lens; move them once
+            caches.advance(input_ids.shape[1])
+            new_caches = caches
         x = self.final_ln(x)
         if self.sequence_parallel:
             x = sp_ops.gather_from_sp_region(x)

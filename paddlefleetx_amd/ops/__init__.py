@@ -55,6 +55,7 @@ from paddlefleetx_amd.ops.functional import (  # noqa: E402,F401
     FusedRMSNorm,
     bias_gelu,
     cross_entropy,
+    decode_attention,
     flash_attention,
     flash_attention_packed,
     fused_adamw_flat,

@@ -142,6 +142,35 @@ def attention_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor,
     return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
 
 
+def decode_attention(qkv: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, seq_lens: torch.Tensor,
+                     scale: Optional[float] = None) -> torch.Tensor:
+    """Single-token attention over a preallocated cache, fp32 math.
+
+    qkv [B, 1, h, 3, D] (new token); k_cache/v_cache [B, h, Smax, D] are
+    appended IN PLACE at position seq_lens[b]; positions past it are never
+    read (they may be uninitialised). Returns [B, 1, h*D] in qkv.dtype.
+    """
+    B, _, h, _, D = qkv.shape
+    Smax = k_cache.shape[2]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    q, k_new, v_new = qkv[:, 0, :, 0], qkv[:, 0, :, 1], qkv[:, 0, :, 2]
+    lens = seq_lens.long().clamp(0, Smax - 1)
+    rows = torch.arange(B, device=qkv.device)
+    k_cache[rows, :, lens] = k_new.to(k_cache.dtype)
+    v_cache[rows, :, lens] = v_new.to(v_cache.dtype)
+    valid = (torch.arange(Smax, device=qkv.device)[None, :]
+             <= lens[:, None])[:, None, :]  # [B, 1, Smax]
+    # select, never multiply: the tail may hold NaN/Inf
+    kf = torch.where(valid[..., None], k_cache.float(), 0.0)
+    vf = torch.where(valid[..., None], v_cache.float(), 0.0)
+    s = torch.einsum("bhd,bhsd->bhs", q.float(), kf) * scale
+    s = s.masked_fill(~valid, float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    o = torch.einsum("bhs,bhsd->bhd", p, vf)
+    return o.reshape(B, 1, h * D).to(qkv.dtype)
+
+
 def softmax_causal_fwd(scores: torch.Tensor, scale: float) -> torch.Tensor:
     """Fused scale + causal-mask + softmax on [B, H, Sq, Sk] scores (fp32 math)."""
     s = scores.float() * scale

@@ -307,6 +307,38 @@ def flash_attention_packed(qkv, num_heads: int,
                                     p_drop, seed)
 
 
+def decode_attention(qkv, k_cache, v_cache, seq_lens,
+                     scale: Optional[float] = None,
+                     max_seq_len: Optional[int] = None,
+                     num_splits: Optional[int] = None):
+    """Single-token attention over a preallocated KV cache (inference only).
+
+    qkv [B, 1, h, 3, D] is the fused-QKV linear output of the new token;
+    k_cache/v_cache [B, h, Smax, D] get its K/V appended IN PLACE at
+    position seq_lens[b] (int32 [B], tokens already cached per row, never
+    written here). Returns [B, 1, h*D].
+
+    max_seq_len: host upper bound on max(seq_lens) + 1 (sizes the KV
+    split; default Smax). num_splits: None/0 = automatic, 1..32 forced.
+
+    bf16 CUDA tensors with D in {64, 128} run the HIP kernel (an error if
+    the extension is missing); every other dtype/device/D runs the fp32
+    reference twin, which has the same in-place semantics.
+    """
+    assert not (torch.is_grad_enabled() and (
+        qkv.requires_grad or k_cache.requires_grad or v_cache.requires_grad)), \
+        "decode_attention is inference-only (no autograd)"
+    D = qkv.shape[-1]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if use_hip(qkv) and qkv.dtype == torch.bfloat16 and D in (64, 128):
+        msl = int(max_seq_len) if max_seq_len is not None \
+            else k_cache.shape[2]
+        return hip_ext().decode_attn(qkv, k_cache, v_cache, seq_lens,
+                                     float(scale), msl,
+                                     int(num_splits or 0))
+    return ref.decode_attention(qkv, k_cache, v_cache, seq_lens, scale)
+
+
 # ---------------------------------------------------------------------------
 # Fused scale + causal mask + softmax (non-flash core_attn path)
 # ---------------------------------------------------------------------------
