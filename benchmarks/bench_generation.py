@@ -34,6 +34,10 @@ def main():
     p.add_argument("--static-cache", action="store_true",
                    help="preallocated KV cache + fused decode attention "
                         "(Generation.static_kv_cache)")
+    p.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                   help="storage of the static cache "
+                        "(Generation.kv_cache_dtype); fp8 needs "
+                        "--static-cache")
     args = p.parse_args()
 
     from paddlefleetx_amd.parallel.env import set_hcg
@@ -60,12 +64,14 @@ def main():
             "use_topp_sampling": True,
             "eos_token_id": vocab - 1,
             "static_kv_cache": args.static_cache,
+            "kv_cache_dtype": args.kv_dtype,
         })
     model.eval()
 
     print(f"# decode bench {args.model} prompt={args.prompt_len} "
           f"gen={args.gen_len} top_p={args.top_p} "
-          f"static_cache={args.static_cache} ({dev})")
+          f"static_cache={args.static_cache} kv_dtype={args.kv_dtype} "
+          f"({dev})")
     for bs in [int(b) for b in args.batches.split(",")]:
         ids = torch.randint(0, vocab - 2, (bs, args.prompt_len), device=dev)
         with torch.no_grad():

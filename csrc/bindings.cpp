@@ -72,6 +72,15 @@ torch::Tensor attn_bwd_packed(torch::Tensor dout, torch::Tensor qkv,
 torch::Tensor decode_attn(torch::Tensor qkv, torch::Tensor k_cache,
                           torch::Tensor v_cache, torch::Tensor seq_lens,
                           double scale, long max_seq_len, long num_splits);
+// decode_attention_fp8.hip
+torch::Tensor decode_attn_fp8(torch::Tensor qkv, torch::Tensor k_cache,
+                              torch::Tensor v_cache, torch::Tensor k_scale,
+                              torch::Tensor v_scale, torch::Tensor seq_lens,
+                              double scale, long max_seq_len,
+                              long num_splits);
+void kv_store_fp8(torch::Tensor qkv, torch::Tensor k_cache,
+                  torch::Tensor v_cache, torch::Tensor k_scale,
+                  torch::Tensor v_scale);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -133,6 +142,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("seq_lens"), py::arg("scale"), py::arg("max_seq_len"),
         py::arg("num_splits") = 0);
+  m.def("decode_attn_fp8", &decode_attn_fp8,
+        "decode_attn over an fp8 (e4m3, per-row scale) KV cache; the "
+        "append quantises",
+        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("seq_lens"),
+        py::arg("scale"), py::arg("max_seq_len"), py::arg("num_splits") = 0);
+  m.def("kv_store_fp8", &kv_store_fp8,
+        "prefill store: quantise K/V of packed qkv [B,S,h,3,D] into "
+        "positions [0,S) of an fp8 KV cache",
+        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale"), py::arg("v_scale"));
   m.def("topp_select", &topp_select, "top-p nucleus cutoff + draw");
   m.def("mfma_gemm16_probe", &mfma_gemm16_probe,
         "debug: 16x16x32 MFMA fragment-layout probe");

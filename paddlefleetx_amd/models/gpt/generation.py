@@ -8,7 +8,9 @@ and the hybrid twin hybrid_model.py:1209.
 MI355X-native notes: the decode loop runs the same GPTModel with per-layer
 KV caches ([B, H, S, D] tensors grown by concat, or with `static_kv_cache`
 one preallocated StaticKVCache appended in place by the fused decode
-attention kernel, csrc/decode_attention.hip); sampling post-processing
+attention kernel, csrc/decode_attention.hip; `kv_cache_dtype: fp8` stores
+that cache as e4m3 codes with a per-row scale, csrc/decode_attention_fp8.hip);
+sampling post-processing
 uses the hand-written gfx950 top-p kernel (csrc/topp.hip) when
 `use_topp_sampling` is on, replacing the reference's CUB-based
 ppfleetx/ops/topp_sampling.cu.
@@ -73,6 +75,17 @@ class GPTForGeneration(nn.Module):
         self.pad_token_id = int(cfg.get("pad_token_id", 0))
         self.num_return_sequences = int(cfg.get("num_return_sequences", 1))
         self.static_kv_cache = bool(cfg.get("static_kv_cache", False))
+        # storage of the static cache: "bf16" (the model dtype) or "fp8"
+        # (e4m3 codes + one fp32 scale per cached row)
+        self.kv_cache_dtype = str(cfg.get("kv_cache_dtype") or "bf16")
+        if self.kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError(
+                "Generation.kv_cache_dtype must be 'bf16' or 'fp8', got "
+                f"{self.kv_cache_dtype!r}")
+        if self.kv_cache_dtype == "fp8" and not self.static_kv_cache:
+            raise ValueError(
+                "Generation.kv_cache_dtype: fp8 needs static_kv_cache: true "
+                "(the tuple cache has no fp8 mode)")
 
     # -- one forward --------------------------------------------------------
     def _logits(self, input_ids, position_ids, caches):
@@ -88,7 +101,8 @@ class GPTForGeneration(nn.Module):
         attn = self.gpt.layers[0].attn
         return StaticKVCache(len(self.gpt.layers), batch_size,
                              attn.num_heads_local, max_len, attn.head_dim,
-                             dtype=attn.qkv.weight.dtype, device=device)
+                             dtype=attn.qkv.weight.dtype, device=device,
+                             kv_dtype=self.kv_cache_dtype)
 
     def sample(self, input_ids: torch.Tensor,
                logits_processors=None) -> torch.Tensor:

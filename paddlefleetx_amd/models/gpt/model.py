@@ -25,7 +25,7 @@ from torch.utils.checkpoint import checkpoint
 from paddlefleetx_amd.ops import (FusedLayerNorm, bias_gelu,
                                   decode_attention, flash_attention,
                                   flash_attention_packed,
-                                  fused_softmax_causal)
+                                  fused_softmax_causal, kv_cache_store_fp8)
 from paddlefleetx_amd.parallel.env import get_hcg
 from paddlefleetx_amd.parallel.rng import (checkpoint_rng_context,
                                             model_parallel_rng)
@@ -45,14 +45,21 @@ KVCache = Tuple[torch.Tensor, torch.Tensor]  # ([B,H,S,D] k, [B,H,S,D] v)
 
 
 class StaticKVSlot:
-    """One layer's view of a StaticKVCache: its k/v buffers plus the
-    shared lengths. Layers read `lens`/`max_len`, never write them."""
+    """One layer's view of a StaticKVCache: its k/v buffers (plus the
+    per-row scales of an fp8 cache, else None) and the shared lengths.
+    Layers read `lens`/`max_len`, never write them."""
 
-    __slots__ = ("owner", "k", "v")
+    __slots__ = ("owner", "k", "v", "k_scale", "v_scale")
 
     def __init__(self, owner: "StaticKVCache", k: torch.Tensor,
-                 v: torch.Tensor):
+                 v: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
+                 v_scale: Optional[torch.Tensor] = None):
         self.owner, self.k, self.v = owner, k, v
+        self.k_scale, self.v_scale = k_scale, v_scale
+
+    @property
+    def fp8(self) -> bool:
+        return self.k_scale is not None
 
 
 class StaticKVCache:
@@ -63,24 +70,52 @@ class StaticKVCache:
     device int32 lens[B] and a host-side max_len counter. Indexing gives
     layer i its slot; GPTModel.forward calls advance() once per forward,
     after the layer loop, so every layer of a step sees the same lengths.
+
+    kv_dtype None/"bf16": the buffers have `dtype`. "fp8": they hold
+    float8_e4m3fn codes and per-layer k_scale/v_scale [B, h_local, Smax]
+    fp32 carry one scale per cached row, D + 4 bytes per row instead of
+    2*D (`dtype` is then not used).
     """
 
     def __init__(self, num_layers: int, batch_size: int, num_heads: int,
                  max_len: int, head_dim: int,
-                 dtype: Optional[torch.dtype] = None, device=None):
+                 dtype: Optional[torch.dtype] = None, device=None,
+                 kv_dtype: Optional[str] = None):
+        assert kv_dtype in (None, "bf16", "fp8"), \
+            f"StaticKVCache: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}"
+        self.kv_dtype = "fp8" if kv_dtype == "fp8" else "bf16"
         self.capacity = int(max_len)
         shape = (batch_size, num_heads, self.capacity, head_dim)
+        if self.kv_dtype == "fp8":
+            dtype = torch.float8_e4m3fn
         self.k = [torch.empty(shape, dtype=dtype, device=device)
                   for _ in range(num_layers)]
         self.v = [torch.empty(shape, dtype=dtype, device=device)
                   for _ in range(num_layers)]
+        self.k_scale = self.v_scale = None
+        if self.kv_dtype == "fp8":
+            self.k_scale = [torch.empty(shape[:3], dtype=torch.float32,
+                                        device=device)
+                            for _ in range(num_layers)]
+            self.v_scale = [torch.empty(shape[:3], dtype=torch.float32,
+                                        device=device)
+                            for _ in range(num_layers)]
         self.lens = torch.zeros(batch_size, dtype=torch.int32, device=device)
         self.max_len = 0  # host mirror of max(lens)
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the K/V buffers (and scales) over all layers."""
+        bufs = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        return sum(t.numel() * t.element_size() for t in bufs)
 
     def __len__(self) -> int:
         return len(self.k)
 
     def __getitem__(self, i: int) -> StaticKVSlot:
+        if self.kv_dtype == "fp8":
+            return StaticKVSlot(self, self.k[i], self.v[i], self.k_scale[i],
+                                self.v_scale[i])
         return StaticKVSlot(self, self.k[i], self.v[i])
 
     def advance(self, n: int) -> None:
@@ -238,7 +273,8 @@ class MultiHeadAttention(nn.Module):
         """Inference against a preallocated cache slot. Decode (S == 1) is
         ONE fused kernel on the packed QKV view (in-place append + split-KV
         attention); prefill computes attention as the no-cache forward does
-        and copies K/V into the slot."""
+        and copies K/V into the slot (an fp8 slot: one quantising store;
+        prefill attention still runs on the unquantised qkv)."""
         assert not (self.training and self.attn_dropout_p > 0.0), \
             "StaticKVCache is inference-only (attention dropout is on)"
         B, S, _ = qkv.shape
@@ -248,12 +284,18 @@ class MultiHeadAttention(nn.Module):
             f"StaticKVCache overflow: {n_cached}+{S} > {slot.owner.capacity}"
         if S == 1:
             o = decode_attention(packed, slot.k, slot.v, slot.owner.lens,
-                                 scale=self.scale, max_seq_len=n_cached + 1)
+                                 scale=self.scale, max_seq_len=n_cached + 1,
+                                 k_scale=slot.k_scale, v_scale=slot.v_scale)
             return self.out_proj(o), slot
         assert n_cached == 0, \
             "StaticKVCache prefill (S > 1) needs an empty cache"
-        slot.k[:, :, :S].copy_(packed[:, :, :, 1].transpose(1, 2))
-        slot.v[:, :, :S].copy_(packed[:, :, :, 2].transpose(1, 2))
+        if slot.fp8:
+            # one quantising launch; attention below still runs on bf16 qkv
+            kv_cache_store_fp8(packed, slot.k, slot.v, slot.k_scale,
+                               slot.v_scale)
+        else:
+            slot.k[:, :, :S].copy_(packed[:, :, :, 1].transpose(1, 2))
+            slot.v[:, :, :S].copy_(packed[:, :, :, 2].transpose(1, 2))
         if self.fused_attn:
             o = flash_attention_packed(packed, self.num_heads_local,
                                        scale=self.scale)

@@ -61,6 +61,7 @@ from paddlefleetx_amd.ops.functional import (  # noqa: E402,F401
     fused_adamw_flat,
     fused_softmax_bias,
     fused_softmax_causal,
+    kv_cache_store_fp8,
     layernorm,
     layernorm_residual,
     rmsnorm,

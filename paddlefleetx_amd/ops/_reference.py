@@ -171,6 +171,85 @@ def decode_attention(qkv: torch.Tensor, k_cache: torch.Tensor,
     return o.reshape(B, 1, h * D).to(qkv.dtype)
 
 
+FP8_MAX = 448.0  # largest finite float8_e4m3fn
+
+
+def quantize_kv_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-row fp8 quantisation of the KV cache: x [..., D] -> (codes
+    [..., D] float8_e4m3fn, scale [...] fp32). fp32 arithmetic:
+    amax = max|x|; scale = amax / 448, inv = 448 / amax (both 1 for an
+    all-zero row); code = e4m3_rne(clamp(x * inv, -448, 448)). The clamp
+    comes before the cast, which would turn overflow into NaN."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    nz = amax > 0
+    safe = torch.where(nz, amax, torch.ones_like(amax))
+    scale = torch.where(nz, safe / FP8_MAX, torch.ones_like(amax))
+    inv = torch.where(nz, FP8_MAX / safe, torch.ones_like(amax))
+    codes = (xf * inv[..., None]).clamp(-FP8_MAX, FP8_MAX) \
+        .to(torch.float8_e4m3fn)
+    return codes, scale
+
+
+def dequantize_kv_rows(codes: torch.Tensor, scale: torch.Tensor
+                       ) -> torch.Tensor:
+    """fp32 [..., D] = float(code) * scale of the row."""
+    return codes.float() * scale.float()[..., None]
+
+
+def decode_attention_fp8(qkv: torch.Tensor, k_cache: torch.Tensor,
+                         v_cache: torch.Tensor, k_scale: torch.Tensor,
+                         v_scale: torch.Tensor, seq_lens: torch.Tensor,
+                         scale: Optional[float] = None) -> torch.Tensor:
+    """decode_attention over an fp8 cache, fp32 math.
+
+    k_cache/v_cache [B, h, Smax, D] float8_e4m3fn with k_scale/v_scale
+    [B, h, Smax] fp32. The new token's K/V are quantised by
+    quantize_kv_rows and appended IN PLACE (codes and scales) at position
+    seq_lens[b], but enter the softmax unquantised; positions past it are
+    never read (they may hold NaN codes and NaN scales).
+    """
+    B, _, h, _, D = qkv.shape
+    Smax = k_cache.shape[2]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    q, k_new, v_new = qkv[:, 0, :, 0], qkv[:, 0, :, 1], qkv[:, 0, :, 2]
+    lens = seq_lens.long().clamp(0, Smax - 1)
+    rows = torch.arange(B, device=qkv.device)
+    for cache, scales, new in ((k_cache, k_scale, k_new),
+                               (v_cache, v_scale, v_new)):
+        codes, sc = quantize_kv_rows(new)
+        cache[rows, :, lens] = codes
+        scales[rows, :, lens] = sc
+    pos = torch.arange(Smax, device=qkv.device)[None, :]
+    cached = (pos < lens[:, None])[:, None, :]  # [B, 1, Smax]
+    is_new = (pos == lens[:, None])[:, None, :]
+    # select, never multiply: the tail may hold NaN codes and scales
+    kf = torch.where(cached[..., None], dequantize_kv_rows(k_cache, k_scale),
+                     0.0)
+    vf = torch.where(cached[..., None], dequantize_kv_rows(v_cache, v_scale),
+                     0.0)
+    kf = torch.where(is_new[..., None], k_new.float()[:, :, None], kf)
+    vf = torch.where(is_new[..., None], v_new.float()[:, :, None], vf)
+    s = torch.einsum("bhd,bhsd->bhs", q.float(), kf) * scale
+    s = s.masked_fill(~(cached | is_new), float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    o = torch.einsum("bhs,bhsd->bhd", p, vf)
+    return o.reshape(B, 1, h * D).to(qkv.dtype)
+
+
+def kv_store_fp8(qkv: torch.Tensor, k_cache: torch.Tensor,
+                 v_cache: torch.Tensor, k_scale: torch.Tensor,
+                 v_scale: torch.Tensor) -> None:
+    """Prefill store: quantise K and V of the packed qkv [B, S, h, 3, D]
+    into positions [0, S) of the fp8 caches and their scales, in place."""
+    S = qkv.shape[1]
+    assert S <= k_cache.shape[2], "kv_store_fp8: S must be <= Smax"
+    for cache, scales, which in ((k_cache, k_scale, 1), (v_cache, v_scale, 2)):
+        codes, sc = quantize_kv_rows(qkv[:, :, :, which].transpose(1, 2))
+        cache[:, :, :S].copy_(codes)
+        scales[:, :, :S].copy_(sc)
+
+
 def softmax_causal_fwd(scores: torch.Tensor, scale: float) -> torch.Tensor:
     """Fused scale + causal-mask + softmax on [B, H, Sq, Sk] scores (fp32 math)."""
     s = scores.float() * scale

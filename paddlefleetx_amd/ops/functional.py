@@ -310,7 +310,8 @@ def flash_attention_packed(qkv, num_heads: int,
 def decode_attention(qkv, k_cache, v_cache, seq_lens,
                      scale: Optional[float] = None,
                      max_seq_len: Optional[int] = None,
-                     num_splits: Optional[int] = None):
+                     num_splits: Optional[int] = None,
+                     k_scale=None, v_scale=None):
     """Single-token attention over a preallocated KV cache (inference only).
 
     qkv [B, 1, h, 3, D] is the fused-QKV linear output of the new token;
@@ -324,19 +325,64 @@ def decode_attention(qkv, k_cache, v_cache, seq_lens,
     bf16 CUDA tensors with D in {64, 128} run the HIP kernel (an error if
     the extension is missing); every other dtype/device/D runs the fp32
     reference twin, which has the same in-place semantics.
+
+    float8_e4m3fn caches select the fp8 storage mode and need k_scale/
+    v_scale (fp32 [B, h, Smax], one scale per cached row): the append
+    quantises the new K/V row (ref.quantize_kv_rows) and writes codes and
+    scales at seq_lens[b]; the new token itself enters the softmax
+    unquantised. Same dispatch rule, on the dtype of qkv.
     """
     assert not (torch.is_grad_enabled() and (
         qkv.requires_grad or k_cache.requires_grad or v_cache.requires_grad)), \
         "decode_attention is inference-only (no autograd)"
     D = qkv.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if fp8:
+        assert v_cache.dtype == torch.float8_e4m3fn, \
+            "decode_attention: k_cache is fp8, v_cache is not"
+        assert k_scale is not None and v_scale is not None, \
+            "decode_attention: fp8 caches need k_scale and v_scale"
+    else:
+        assert k_scale is None and v_scale is None, \
+            "decode_attention: k_scale/v_scale go with fp8 caches only"
     if use_hip(qkv) and qkv.dtype == torch.bfloat16 and D in (64, 128):
         msl = int(max_seq_len) if max_seq_len is not None \
             else k_cache.shape[2]
+        if fp8:
+            return hip_ext().decode_attn_fp8(qkv, k_cache, v_cache, k_scale,
+                                             v_scale, seq_lens, float(scale),
+                                             msl, int(num_splits or 0))
         return hip_ext().decode_attn(qkv, k_cache, v_cache, seq_lens,
                                      float(scale), msl,
                                      int(num_splits or 0))
+    if fp8:
+        return ref.decode_attention_fp8(qkv, k_cache, v_cache, k_scale,
+                                        v_scale, seq_lens, scale)
     return ref.decode_attention(qkv, k_cache, v_cache, seq_lens, scale)
+
+
+def kv_cache_store_fp8(qkv, k_cache, v_cache, k_scale, v_scale) -> None:
+    """Prefill store into an fp8 KV cache (inference only).
+
+    qkv [B, S, h, 3, D] is the fused-QKV linear output of the prompt; its K
+    and V rows are quantised (one fp32 scale per row, ref.quantize_kv_rows)
+    into positions [0, S) of k_cache/v_cache [B, h, Smax, D] float8_e4m3fn
+    and k_scale/v_scale [B, h, Smax], in place and in one launch.
+    Positions >= S are not touched.
+
+    Dispatch as decode_attention: bf16 CUDA qkv with D in {64, 128} runs
+    the HIP kernel, everything else the reference twin.
+    """
+    assert not (torch.is_grad_enabled() and qkv.requires_grad), \
+        "kv_cache_store_fp8 is inference-only (no autograd)"
+    assert qkv.shape[1] <= k_cache.shape[2], \
+        "kv_cache_store_fp8: S must be <= Smax"
+    D = qkv.shape[-1]
+    if use_hip(qkv) and qkv.dtype == torch.bfloat16 and D in (64, 128):
+        hip_ext().kv_store_fp8(qkv, k_cache, v_cache, k_scale, v_scale)
+        return
+    ref.kv_store_fp8(qkv, k_cache, v_cache, k_scale, v_scale)
 
 
 # ---------------------------------------------------------------------------
