@@ -5,7 +5,8 @@ Counterpart of the reference's inference latency harness
 (ppfleetx projects/gpt/benchmark.py:44-85: batch sweep, ms/batch print).
 
     python benchmarks/bench_generation.py [--model GPT-1.3B] \
-        [--prompt-len 128] [--gen-len 64]
+        [--prompt-len 128] [--gen-len 64] \
+        [--static-cache [--kv-dtype fp8] [--fused-sampling [--capture]]]
 """
 
 import argparse
@@ -38,7 +39,24 @@ def main():
                    help="storage of the static cache "
                         "(Generation.kv_cache_dtype); fp8 needs "
                         "--static-cache")
+    p.add_argument("--fused-sampling", action="store_true",
+                   help="one sample_token launch per token, no host sync per "
+                        "token (Generation.fused_sampling); needs "
+                        "--static-cache")
+    p.add_argument("--capture", action="store_true",
+                   help="replay a captured decode step per token "
+                        "(Generation.capture_decode); needs --fused-sampling")
+    p.add_argument("--finish-check-interval", type=int, default=None,
+                   help="Generation.finish_check_interval (fused sampling)")
+    p.add_argument("--fixed-capacity", action="store_true",
+                   help="Generation.kv_cache_capacity = prompt + gen: decode "
+                        "attention sizes its split for the capacity at every "
+                        "step, as a captured step does")
     args = p.parse_args()
+    if args.capture and not args.fused_sampling:
+        p.error("--capture needs --fused-sampling")
+    if args.fused_sampling and not args.static_cache:
+        p.error("--fused-sampling needs --static-cache")
 
     from paddlefleetx_amd.parallel.env import set_hcg
     from paddlefleetx_amd.parallel.topology import HybridTopology
@@ -65,12 +83,19 @@ def main():
             "eos_token_id": vocab - 1,
             "static_kv_cache": args.static_cache,
             "kv_cache_dtype": args.kv_dtype,
+            "fused_sampling": args.fused_sampling,
+            "capture_decode": args.capture,
+            **({"finish_check_interval": args.finish_check_interval}
+               if args.finish_check_interval else {}),
+            **({"kv_cache_capacity": args.prompt_len + args.gen_len}
+               if args.fixed_capacity else {}),
         })
     model.eval()
 
     print(f"# decode bench {args.model} prompt={args.prompt_len} "
           f"gen={args.gen_len} top_p={args.top_p} "
           f"static_cache={args.static_cache} kv_dtype={args.kv_dtype} "
+          f"fused_sampling={args.fused_sampling} capture={args.capture} "
           f"({dev})")
     for bs in [int(b) for b in args.batches.split(",")]:
         ids = torch.randint(0, vocab - 2, (bs, args.prompt_len), device=dev)

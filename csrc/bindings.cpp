@@ -85,6 +85,13 @@ void kv_store_fp8(torch::Tensor qkv, torch::Tensor k_cache,
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
                                        torch::Tensor top_p, torch::Tensor u);
+// sample_token.hip
+std::vector<torch::Tensor> sample_token(
+    torch::Tensor logits, torch::Tensor ids_buf, torch::Tensor lens,
+    torch::Tensor unfinished, torch::Tensor u, torch::Tensor next_tokens,
+    bool greedy, double temperature, long top_k, double top_p,
+    double repetition_penalty, long min_length, long eos_token_id,
+    long pad_token_id);
 // moe.hip
 std::vector<torch::Tensor> moe_dispatch(torch::Tensor x,
                                         torch::Tensor expert_ids,
@@ -154,6 +161,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("k_scale"), py::arg("v_scale"));
   m.def("topp_select", &topp_select, "top-p nucleus cutoff + draw");
+  m.def("sample_token", &sample_token,
+        "logits row -> next token in one launch (min length, repetition "
+        "penalty, temperature, softmax, top-k, top-p, draw, finish); "
+        "returns (kept_count, kept_mass)",
+        py::arg("logits"), py::arg("ids_buf"), py::arg("lens"),
+        py::arg("unfinished"), py::arg("u"), py::arg("next_tokens"),
+        py::arg("greedy"), py::arg("temperature"), py::arg("top_k"),
+        py::arg("top_p"), py::arg("repetition_penalty"),
+        py::arg("min_length"), py::arg("eos_token_id"),
+        py::arg("pad_token_id"));
   m.def("mfma_gemm16_probe", &mfma_gemm16_probe,
         "debug: 16x16x32 MFMA fragment-layout probe");
 }

@@ -14,6 +14,12 @@ sampling post-processing
 uses the hand-written gfx950 top-p kernel (csrc/topp.hip) when
 `use_topp_sampling` is on, replacing the reference's CUB-based
 ppfleetx/ops/topp_sampling.cu.
+
+`fused_sampling: true` (needs the static cache) replaces the whole sampling
+tail by ONE launch per token (csrc/sample_token.hip) that also keeps the
+generation state on the device, so the loop has no host synchronisation
+per token; `capture_decode: true` on top of it records one decode step
+(forward + sampler) as a graph and replays it once per token.
 """
 
 from __future__ import annotations
@@ -26,8 +32,10 @@ import torch.nn.functional as F
 
 from paddlefleetx_amd.models.gpt.model import GPTModel, StaticKVCache
 from paddlefleetx_amd.models.gpt.processor import get_logits_processor
-from paddlefleetx_amd.ops import topp_sampling
+from paddlefleetx_amd.ops import sample_token, topp_sampling
+from paddlefleetx_amd.parallel.env import get_hcg
 from paddlefleetx_amd.parallel.tp import parallel_matmul
+from paddlefleetx_amd.utils.log import logger
 
 
 def TopKProcess(probs: torch.Tensor, top_k: int, min_tokens_to_keep: int = 1
@@ -86,6 +94,33 @@ class GPTForGeneration(nn.Module):
             raise ValueError(
                 "Generation.kv_cache_dtype: fp8 needs static_kv_cache: true "
                 "(the tuple cache has no fp8 mode)")
+        # one sample_token launch per token, state on the device
+        self.fused_sampling = bool(cfg.get("fused_sampling", False))
+        if self.fused_sampling and not self.static_kv_cache:
+            raise ValueError(
+                "Generation.fused_sampling: true needs static_kv_cache: true "
+                "(the sampler reads the static cache's device lens)")
+        # the all-finished test (the loop's only host sync) runs every this
+        # many tokens; the result is trimmed to what a per-token test gives
+        self.finish_check_interval = int(cfg.get("finish_check_interval", 4))
+        if self.finish_check_interval < 1:
+            raise ValueError(
+                "Generation.finish_check_interval must be >= 1, got "
+                f"{self.finish_check_interval}")
+        # optional fixed capacity of the static cache (default: prompt +
+        # max_dec_len per call). When set, decode attention sizes its KV
+        # split for this capacity at every step, so an eager and a captured
+        # run make the same split choice.
+        cap = cfg.get("kv_cache_capacity")
+        self.kv_cache_capacity = int(cap) if cap else None
+        # replay one captured decode step per token (see _sample_captured)
+        self.capture_decode = bool(cfg.get("capture_decode", False))
+        self._capture_warned = False
+        if self.capture_decode and not self.fused_sampling:
+            logger.warning("Generation.capture_decode needs fused_sampling: "
+                           "true: staying eager")
+            self.capture_decode = False
+        self._graph_state = None
 
     # -- one forward --------------------------------------------------------
     def _logits(self, input_ids, position_ids, caches):
@@ -96,17 +131,202 @@ class GPTForGeneration(nn.Module):
             parallel_output=False)
         return logits.float(), new_caches
 
-    def _new_static_cache(self, batch_size: int, max_len: int, device
-                          ) -> StaticKVCache:
+    def _new_static_cache(self, batch_size: int, max_len: int, device,
+                          max_seq_len: Optional[int] = None) -> StaticKVCache:
         attn = self.gpt.layers[0].attn
         return StaticKVCache(len(self.gpt.layers), batch_size,
                              attn.num_heads_local, max_len, attn.head_dim,
                              dtype=attn.qkv.weight.dtype, device=device,
-                             kv_dtype=self.kv_cache_dtype)
+                             kv_dtype=self.kv_cache_dtype,
+                             max_seq_len=max_seq_len)
+
+    # -- fused sampling -----------------------------------------------------
+    def _capacity(self, prompt_len: int) -> int:
+        need = prompt_len + self.max_length
+        if self.kv_cache_capacity is None:
+            return need
+        if self.kv_cache_capacity < need:
+            raise ValueError(
+                f"Generation.kv_cache_capacity {self.kv_cache_capacity} < "
+                f"prompt {prompt_len} + max_dec_len {self.max_length}")
+        return self.kv_cache_capacity
+
+    def _sampler_args(self, prompt_len: int) -> dict:
+        return dict(greedy=self.decode_strategy == "greedy_search",
+                    temperature=self.temperature, top_k=self.top_k,
+                    top_p=self.top_p,
+                    repetition_penalty=self.repetition_penalty,
+                    min_length=(prompt_len + self.min_length
+                                if self.min_length > 0 else 0),
+                    eos_token_id=self.eos_token_id,
+                    pad_token_id=self.pad_token_id)
+
+    def _decode_step(self, st: dict, kw: dict) -> None:
+        """One decode step on device state only: forward of next_tokens at
+        position lens (which advances lens), logits, sample_token."""
+        cache = st["cache"]
+        pos = cache.lens.long().unsqueeze(1)
+        hidden, _ = self.gpt(st["next_tokens"], pos, caches=cache,
+                             use_cache=True)
+        logits = parallel_matmul(
+            hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight,
+            parallel_output=False)
+        sample_token(logits, st["ids_buf"], cache.lens, st["unfinished"],
+                     st["u"], st["next_tokens"], **kw)
+
+    def _new_state(self, B: int, capacity: int, device, fixed: bool) -> dict:
+        return dict(
+            cache=self._new_static_cache(
+                B, capacity, device, max_seq_len=capacity if fixed else None),
+            ids_buf=torch.empty(B, capacity, dtype=torch.long, device=device),
+            unfinished=torch.empty(B, dtype=torch.bool, device=device),
+            next_tokens=torch.empty(B, 1, dtype=torch.long, device=device),
+            u=torch.zeros(B, capacity, dtype=torch.float32, device=device))
+
+    def _start(self, st: dict, input_ids: torch.Tensor, kw: dict) -> None:
+        """Reset the state, prefill eagerly and sample the first token."""
+        B, prompt_len = input_ids.shape
+        n = prompt_len + self.max_length
+        cache = st["cache"]
+        cache.lens.zero_()
+        cache.max_len = 0
+        st["ids_buf"].fill_(self.pad_token_id)
+        st["ids_buf"][:, :prompt_len] = input_ids
+        st["unfinished"].fill_(True)
+        # the only RNG use of a call: seeding reproduces a run, and the draw
+        # does not depend on the capacity of the buffers
+        st["u"][:, :n] = torch.rand(B, n, device=input_ids.device)
+        position_ids = torch.arange(prompt_len, device=input_ids.device) \
+            .unsqueeze(0).expand(B, -1)
+        hidden, _ = self.gpt(input_ids, position_ids, caches=cache,
+                             use_cache=True)
+        logits = parallel_matmul(
+            hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight,
+            parallel_output=False)
+        sample_token(logits, st["ids_buf"], cache.lens, st["unfinished"],
+                     st["u"], st["next_tokens"], **kw)
+
+    def _trim(self, st: dict, prompt_len: int, n_done: int) -> torch.Tensor:
+        """What the per-token loop returns: it stops at the step where the
+        last row finishes; rows that finished earlier are padded."""
+        out = st["ids_buf"][:, prompt_len:prompt_len + n_done]
+        is_eos = out == self.eos_token_id
+        # step at which each row finished (its first eos), n_done if never
+        first = torch.where(is_eos.any(-1),
+                            is_eos.to(torch.int8).argmax(-1) + 1,
+                            torch.full((out.shape[0],), n_done,
+                                       device=out.device))
+        return out[:, :int(first.max())].clone()
+
+    def _sample_fused(self, input_ids: torch.Tensor,
+                      return_state: bool = False):
+        """The loop of sample() with the tail fused into sample_token and no
+        host synchronisation per token. return_state also hands back the
+        device state (cache, ids_buf, ...) the call ended with."""
+        B, prompt_len = input_ids.shape
+        kw = self._sampler_args(prompt_len)
+        if self._use_capture(input_ids):
+            out = self._sample_captured(input_ids, kw)
+            return (out, self._graph_state) if return_state else out
+        st = self._new_state(B, self._capacity(prompt_len), input_ids.device,
+                             fixed=self.kv_cache_capacity is not None)
+        self._start(st, input_ids, kw)
+        n_done = 1
+        while n_done < self.max_length:
+            if n_done % self.finish_check_interval == 0 and \
+                    not st["unfinished"].any():
+                break
+            self._decode_step(st, kw)
+            n_done += 1
+        out = self._trim(st, prompt_len, n_done)
+        return (out, st) if return_state else out
+
+    # -- captured decode step -------------------------------------------------
+    def _use_capture(self, input_ids: torch.Tensor) -> bool:
+        if not self.capture_decode:
+            return False
+        why = None
+        if input_ids.device.type != "cuda":
+            why = "needs a CUDA device"
+        elif get_hcg().get_model_parallel_world_size() != 1:
+            why = "needs model-parallel size 1"
+        if why is not None:
+            if not self._capture_warned:
+                logger.warning(
+                    f"Generation.capture_decode {why}: staying eager")
+                self._capture_warned = True
+            return False
+        return True
+
+    def _build_graph(self, B: int, capacity: int, device, kw: dict) -> dict:
+        """Allocate the fixed-address state and record ONE decode step on one
+        stream (no parallel branches). The graph bakes in the sampler
+        scalars, so they are part of the reuse key."""
+        st = self._new_state(B, capacity, device, fixed=True)
+        cache = st["cache"]
+
+        def reset():
+            cache.lens.zero_()
+            cache.max_len = 0
+            st["ids_buf"].fill_(self.pad_token_id)
+            st["unfinished"].fill_(True)
+            st["next_tokens"].zero_()
+
+        reset()
+        # eager warm-up against the empty cache (L = 0 is a valid shape):
+        # library handles, workspaces and the allocator settle before capture
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._decode_step(st, kw)
+        torch.cuda.current_stream().wait_stream(side)
+        reset()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._decode_step(st, kw)
+        reset()
+        st.update(graph=graph, key=(B, tuple(sorted(kw.items()))))
+        logger.info(f"decode step captured (B={B}, capacity={capacity})")
+        return st
+
+    def _sample_captured(self, input_ids: torch.Tensor, kw: dict
+                         ) -> torch.Tensor:
+        B, prompt_len = input_ids.shape
+        capacity = self._capacity(prompt_len)
+        # min_length moves with the prompt length and is baked into the graph
+        key = (B, tuple(sorted(kw.items())))
+        st = self._graph_state
+        if st is None or st["key"] != key or \
+                st["cache"].capacity < capacity:
+            self._graph_state = None  # free the old buffers first
+            st = self._graph_state = self._build_graph(
+                B, capacity, input_ids.device, kw)
+        cache = st["cache"]
+        self._start(st, input_ids, kw)
+        n_done = 1
+        while n_done < self.max_length:
+            if n_done % self.finish_check_interval == 0 and \
+                    not st["unfinished"].any():
+                break
+            # the recorded advance moves only the device lens
+            assert cache.max_len + 1 <= cache.capacity, \
+                f"StaticKVCache overflow: {cache.max_len}+1 > {cache.capacity}"
+            st["graph"].replay()
+            cache.max_len += 1
+            n_done += 1
+        return self._trim(st, prompt_len, n_done)
 
     def sample(self, input_ids: torch.Tensor,
                logits_processors=None) -> torch.Tensor:
         """Autoregressive sampling loop (single_model.py:1139-1320)."""
+        if self.fused_sampling:
+            if logits_processors is not None:
+                raise ValueError(
+                    "Generation.fused_sampling does not support user-supplied "
+                    "logits_processors (the fused sampler applies min length "
+                    "and the repetition penalty itself)")
+            return self._sample_fused(input_ids)
         B, prompt_len = input_ids.shape
         device = input_ids.device
         processors = logits_processors if logits_processors is not None else \

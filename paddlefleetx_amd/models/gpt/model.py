@@ -75,16 +75,26 @@ class StaticKVCache:
     float8_e4m3fn codes and per-layer k_scale/v_scale [B, h_local, Smax]
     fp32 carry one scale per cached row, D + 4 bytes per row instead of
     2*D (`dtype` is then not used).
+
+    max_seq_len (optional, in [1, max_len]): a FIXED bound that decode
+    attention sizes its KV split for, in place of the host counter + 1. The
+    kernel clamps per row, so this costs balance, not correctness; it makes
+    the split choice independent of the step, which a captured decode step
+    needs (and an eager run can share).
     """
 
     def __init__(self, num_layers: int, batch_size: int, num_heads: int,
                  max_len: int, head_dim: int,
                  dtype: Optional[torch.dtype] = None, device=None,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None,
+                 max_seq_len: Optional[int] = None):
         assert kv_dtype in (None, "bf16", "fp8"), \
             f"StaticKVCache: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}"
         self.kv_dtype = "fp8" if kv_dtype == "fp8" else "bf16"
         self.capacity = int(max_len)
+        assert max_seq_len is None or 1 <= int(max_seq_len) <= self.capacity, \
+            f"StaticKVCache: max_seq_len {max_seq_len} not in [1, {max_len}]"
+        self.max_seq_len = None if max_seq_len is None else int(max_seq_len)
         shape = (batch_size, num_heads, self.capacity, head_dim)
         if self.kv_dtype == "fp8":
             dtype = torch.float8_e4m3fn
@@ -284,7 +294,9 @@ class MultiHeadAttention(nn.Module):
             f"StaticKVCache overflow: {n_cached}+{S} > {slot.owner.capacity}"
         if S == 1:
             o = decode_attention(packed, slot.k, slot.v, slot.owner.lens,
-                                 scale=self.scale, max_seq_len=n_cached + 1,
+                                 scale=self.scale,
+                                 max_seq_len=slot.owner.max_seq_len
+                                 or n_cached + 1,
                                  k_scale=slot.k_scale, v_scale=slot.v_scale)
             return self.out_proj(o), slot
         assert n_cached == 0, \

@@ -66,5 +66,6 @@ from paddlefleetx_amd.ops.functional import (  # noqa: E402,F401
     layernorm_residual,
     rmsnorm,
     rope,
+    sample_token,
     topp_sampling,
 )

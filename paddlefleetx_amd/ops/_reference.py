@@ -352,3 +352,91 @@ def topp_sampling(probs: torch.Tensor, top_p: torch.Tensor,
     ids = sorted_idx.gather(1, pick)
     pp = probs.gather(1, ids)
     return ids, pp
+
+
+def sample_token_filter(logits: torch.Tensor, ids_buf: torch.Tensor,
+                        lens: torch.Tensor, temperature: float = 1.0,
+                        top_k: int = 0, top_p: float = 1.0,
+                        repetition_penalty: float = 1.0, min_length: int = 0,
+                        eos_token_id: int = -1
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Steps 1-6 of sample_token: (processed logits, probs, keep), all [B, V].
+
+    processed: fp32 logits after the min-length mask and the repetition
+    penalty (before temperature). probs: softmax(processed / temperature).
+    keep: the tokens that survive top-k and top-p. Top-p is tie-inclusive:
+    every token equal in probability to the last one of the sorted nucleus
+    is kept, where the sort in TopPProcess keeps an arbitrary subset of a
+    tie. A zero-probability token is never kept.
+    """
+    x = logits.float().clone()
+    B, V = x.shape
+    T = ids_buf.shape[1]
+    L = lens.long().clamp(0, T)
+    if 0 <= eos_token_id < V:
+        x[:, eos_token_id] = torch.where(
+            L < min_length, torch.full_like(x[:, eos_token_id], -math.inf),
+            x[:, eos_token_id])
+    if repetition_penalty != 1.0:
+        valid = (torch.arange(T, device=x.device)[None] < L[:, None]) \
+            & (ids_buf >= 0) & (ids_buf < V)
+        seen = torch.zeros(B, V, dtype=torch.int32, device=x.device)
+        seen.scatter_add_(1, ids_buf.clamp(0, V - 1), valid.to(torch.int32))
+        x = torch.where(seen > 0,
+                        torch.where(x < 0, x * repetition_penalty,
+                                    x / repetition_penalty), x)
+    probs = F.softmax(x / temperature if temperature != 1.0 else x, dim=-1)
+    q = probs
+    if 0 < top_k < V:
+        kth = torch.topk(q, top_k, dim=-1).values[:, -1:]
+        q = torch.where(q >= kth, q, torch.zeros_like(q))
+    if top_p < 1.0:
+        sorted_q, _ = torch.sort(q, dim=-1, descending=True)
+        # shortest prefix whose mass exceeds top_p: sorted token j stays
+        # while the mass ahead of it does not (cumsum is monotone, so the
+        # kept positions are a prefix)
+        ahead = torch.cumsum(sorted_q, dim=-1).roll(1, -1)
+        ahead[:, 0] = 0.0
+        ncut = (ahead <= max(top_p, 0.0)).sum(-1, keepdim=True)
+        last = sorted_q.gather(1, ncut - 1)
+        q = torch.where(q >= last, q, torch.zeros_like(q))
+    return x, probs, q > 0
+
+
+def sample_token(logits: torch.Tensor, ids_buf: torch.Tensor,
+                 lens: torch.Tensor, unfinished: torch.Tensor,
+                 u: torch.Tensor, next_tokens: torch.Tensor,
+                 greedy: bool = False, temperature: float = 1.0,
+                 top_k: int = 0, top_p: float = 1.0,
+                 repetition_penalty: float = 1.0, min_length: int = 0,
+                 eos_token_id: int = -1, pad_token_id: int = 0
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 twin of csrc/sample_token.hip; see ops.sample_token. Only tensor
+    ops on the inputs' device, no host synchronisation."""
+    B, V = logits.shape
+    T = ids_buf.shape[1]
+    L = lens.long().clamp(0, T)
+    x, probs, keep = sample_token_filter(
+        logits, ids_buf, lens, temperature, top_k, top_p, repetition_penalty,
+        min_length, eos_token_id)
+    if greedy:
+        pick = x.argmax(dim=-1)
+        count = torch.ones(B, dtype=torch.int32, device=x.device)
+        mass = torch.zeros(B, dtype=torch.float32, device=x.device)
+    else:
+        kept = torch.where(keep, probs, torch.zeros_like(probs))
+        cum = torch.cumsum(kept, dim=-1)  # inclusive, vocabulary order
+        mass = cum[:, -1].clone()
+        uu = u.gather(1, L.clamp(max=T - 1)[:, None])[:, 0]
+        target = torch.minimum(uu * mass, mass)
+        reach = (cum >= target[:, None]) & (cum > 0)
+        pick = reach.to(torch.int8).argmax(dim=-1)  # first True
+        count = keep.sum(-1).to(torch.int32)
+    unf = unfinished.bool()
+    tok = torch.where(unf, pick, torch.full_like(pick, pad_token_id))
+    slot = L.clamp(max=T - 1)[:, None]
+    ids_buf.scatter_(1, slot, torch.where(L < T, tok,
+                                          ids_buf.gather(1, slot)[:, 0])[:, None])
+    next_tokens.copy_(tok.view_as(next_tokens))
+    unfinished.copy_((unf & (tok != eos_token_id)).to(unfinished.dtype))
+    return count, mass

@@ -590,3 +590,71 @@ def topp_sampling(probs: torch.Tensor, top_p: torch.Tensor, seed: int = -1
                                         u.contiguous())
         return ids, pp.to(probs.dtype)
     return ref.topp_sampling(probs, top_p, seed)
+
+
+# ---------------------------------------------------------------------------
+# Fused sampler: logits row -> next token + generation state, one launch
+# ---------------------------------------------------------------------------
+
+SAMPLE_TOKEN_MAX_VOCAB = 65536
+
+
+def sample_token(logits: torch.Tensor, ids_buf: torch.Tensor,
+                 lens: torch.Tensor, unfinished: torch.Tensor,
+                 u: torch.Tensor, next_tokens: torch.Tensor, *,
+                 greedy: bool = False, temperature: float = 1.0,
+                 top_k: int = 0, top_p: float = 1.0,
+                 repetition_penalty: float = 1.0, min_length: int = 0,
+                 eos_token_id: int = -1, pad_token_id: int = 0
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Turn one row of logits per sequence into its next token, on the
+    device and in place (inference only).
+
+    logits [B, V] fp32 or bf16 (row stride allowed); ids_buf [B, T] int64
+    holds prompt + generated tokens; lens [B] int32 is the number of tokens
+    written so far per row (read only: the KV cache's own tensor);
+    unfinished [B] bool/uint8 is updated in place; u [B, T] fp32 uniforms in
+    [0, 1), row b uses u[b, lens[b]]; next_tokens [B, 1] int64 is written.
+    Returns (kept_count [B] int32, kept_mass [B] fp32), the size and the
+    unrenormalised mass of the set the token was drawn from (greedy: 1, 0).
+
+    Per row, in the order of the eager loop in GPTForGeneration.sample:
+      1. lens[b] < min_length: the eos logit is -inf;
+      2. every distinct token of ids_buf[b, :lens[b]] gets
+         x < 0 ? x * penalty : x / penalty, from the original logit;
+      3. divide by temperature; 4. softmax in fp32;
+      5. top-k (0 < top_k < V): keep p >= k-th largest p, ties kept, no
+         renormalisation (TopKProcess);
+      6. top-p (< 1) on those unrenormalised probabilities: the shortest
+         descending prefix whose mass exceeds top_p (TopPProcess), PLUS
+         every token equal in probability to the last one kept. This
+         tie-inclusive rule is the one deliberate deviation from the
+         sort-based TopPProcess, which keeps an arbitrary subset of a tie.
+         At least one token is kept;
+      7. target = u * kept_mass; the first token in vocabulary order whose
+         inclusive kept mass reaches target is picked (the distribution of
+         a draw in sorted order, without a sort). A zero-probability token
+         is never picked. greedy=True takes the arg-max of the logits of
+         step 2 in place of steps 3-7;
+      8. tok = unfinished[b] ? pick : pad; ids_buf[b, lens[b]] = tok (if
+         lens[b] < T); next_tokens[b] = tok; unfinished[b] &= tok != eos.
+
+    CUDA logits with V <= 65536 run the gfx950 kernel (an error if the
+    extension is missing): one workgroup per row, no sort, no workspace,
+    bit-reproducible. Everything else runs the fp32 reference twin.
+    """
+    assert not (torch.is_grad_enabled() and logits.requires_grad), \
+        "sample_token is inference-only (no autograd)"
+    if (use_hip(logits) and logits.dtype in (torch.float32, torch.bfloat16)
+            and logits.shape[-1] <= SAMPLE_TOKEN_MAX_VOCAB):
+        count, mass = hip_ext().sample_token(
+            logits, ids_buf, lens, unfinished, u, next_tokens, bool(greedy),
+            float(temperature), int(top_k), float(top_p),
+            float(repetition_penalty), int(min_length), int(eos_token_id),
+            int(pad_token_id))
+        return count, mass
+    return ref.sample_token(logits, ids_buf, lens, unfinished, u, next_tokens,
+                            bool(greedy), float(temperature), int(top_k),
+                            float(top_p), float(repetition_penalty),
+                            int(min_length), int(eos_token_id),
+                            int(pad_token_id))
