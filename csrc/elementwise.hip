@@ -1,6 +1,7 @@
 // Elementwise fused kernels: bias+gelu (fwd/bwd), flat AdamW, RoPE.
 // All memory-bound: vectorized loads (G13), grid-stride (G11).
 #include "common.h"
+#include "tensor_checks.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -11,8 +12,12 @@ constexpr int BLOCK = 256;
 constexpr float GELU_K = 0.7978845608028654f;  // sqrt(2/pi)
 
 // tanh via the hardware exp unit: tanh(y) = 1 - 2/(exp(2y)+1).
-// libm tanhf lowers to a branchy polynomial (~20 VALU ops); this is 4,
-// exact to ~1 ulp fp32 for the gelu argument range.
+// libm tanhf lowers to a branchy polynomial (~20 VALU ops); this is 4.
+// Its ABSOLUTE error is ~1e-7 (one ulp of the 1 it is subtracted from),
+// so the relative error grows as 1/|y| towards 0: ~1e-5 at y = 1e-3,
+// ~1e-4 at y = 1e-4 (fp32 emulation of the formula against float64
+// tanh). GELU only uses 1 + t and 1 - t*t, where that is harmless; do
+// not reuse this where tanh(y) itself matters for small y.
 DEV_INLINE float fast_tanh(float y) {
   return 1.f - 2.f / (__expf(2.f * y) + 1.f);
 }
@@ -99,10 +104,14 @@ __global__ __launch_bounds__(BLOCK) void colsum_kernel(
 // ---- fused grad sumsq (found_inf + global-norm in ONE pass) ----
 // out[slot] += sum(x^2) in fp32; NaN/Inf grads propagate into the sum,
 // so !isfinite(out) IS the found_inf flag (reference
-// check_finite_and_unscale, distributed/apis/amp.py:212-216)
+// check_finite_and_unscale, distributed/apis/amp.py:212-216).
+// Each block leaves its partial in partial[blockIdx.x]; one small block
+// then adds them up in double and updates out[slot] ONCE. Up to 2048
+// fp32 atomics onto the growing total lost ~1e-6 of it, in an order
+// that changed from run to run.
 template <typename T>
 __global__ void grad_sumsq_kernel(const T* __restrict__ x, long n,
-                                  float* __restrict__ out, long slot) {
+                                  float* __restrict__ partial) {
   __shared__ float sred[BLOCK / WAVE];
   float s = 0.f;
   constexpr int V = 4;
@@ -114,7 +123,26 @@ __global__ void grad_sumsq_kernel(const T* __restrict__ x, long n,
     for (int j = 0; j < V; ++j) s += v[j] * v[j];
   }
   s = block_reduce_sum<BLOCK>(s, sred);
-  if (threadIdx.x == 0) atomicAdd(&out[slot], s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// single block: out[slot] += sum(partial[0 .. np))
+__global__ __launch_bounds__(BLOCK) void grad_sumsq_finish_kernel(
+    const float* __restrict__ partial, int np, float* __restrict__ out,
+    long slot) {
+  __shared__ double sred[BLOCK / WAVE];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < np; i += BLOCK) s += (double)partial[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, WAVE);
+  if (threadIdx.x % WAVE == 0) sred[threadIdx.x / WAVE] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / WAVE; ++w) t += sred[w];
+    out[slot] = (float)((double)out[slot] + t);
+  }
 }
 
 void launch_colsum(const void* x, float* out, long N, int H, bool bf16,
@@ -228,12 +256,17 @@ long grid_for(long total, int per_block) {
 }  // namespace
 
 torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor bias) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() >= 1, "x must have a last dim");
   long total = x.numel();
   int H = x.size(-1);
   long N = total / H;
   TORCH_CHECK(H % 4 == 0, "last dim must be divisible by 4");
   bool has_bias = bias.defined() && bias.numel() > 0;
+  if (has_bias) {
+    fleetx::check_same(bias, x, "bias");
+    fleetx::check_numel(bias, H, "bias");
+  }
   auto y = torch::empty_like(x);
   auto stream = at::hip::getCurrentHIPStream();
   bool v8 = H % 8 == 0;
@@ -260,12 +293,19 @@ torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor bias) {
 
 std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
                                          torch::Tensor bias) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous());
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() >= 1, "x must have a last dim");
+  fleetx::check_same(dy, x, "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "dy must have the shape of x");
   long total = x.numel();
   int H = x.size(-1);
   long N = total / H;
   TORCH_CHECK(H % 4 == 0, "last dim must be divisible by 4");
   bool has_bias = bias.defined() && bias.numel() > 0;
+  if (has_bias) {
+    fleetx::check_same(bias, x, "bias");
+    fleetx::check_numel(bias, H, "bias");
+  }
   auto dx = torch::empty_like(x);
   auto stream = at::hip::getCurrentHIPStream();
   bool v8 = H % 8 == 0;
@@ -300,26 +340,34 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
 
 // accumulate sum(x^2) into out[slot] (fp32). x flat, numel % 4 == 0.
 void grad_sumsq(torch::Tensor x, torch::Tensor out, long slot) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
-  TORCH_CHECK(out.scalar_type() == torch::kFloat);
+  fleetx::check_data(x, "x");
+  fleetx::check_aux(out, torch::kFloat, x, "out");
+  TORCH_CHECK(slot >= 0 && slot < out.numel(), "slot ", slot,
+              " is outside out (", out.numel(), " slots)");
   long n = x.numel();
-  TORCH_CHECK(n % 4 == 0);
+  TORCH_CHECK(n % 4 == 0, "x.numel() must be divisible by 4");
+  if (n == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
   dim3 grid(grid_for(n, BLOCK * 4));
+  auto partial = torch::empty({(long)grid.x}, out.options());
   if (x.scalar_type() == torch::kBFloat16)
     hipLaunchKernelGGL((grad_sumsq_kernel<__hip_bfloat16>), grid,
                        dim3(BLOCK), 0, stream,
                        (const __hip_bfloat16*)x.data_ptr(), n,
-                       out.data_ptr<float>(), slot);
+                       partial.data_ptr<float>());
   else
     hipLaunchKernelGGL((grad_sumsq_kernel<float>), grid, dim3(BLOCK), 0,
                        stream, (const float*)x.data_ptr(), n,
-                       out.data_ptr<float>(), slot);
+                       partial.data_ptr<float>());
+  hipLaunchKernelGGL(grad_sumsq_finish_kernel, dim3(1), dim3(BLOCK), 0,
+                     stream, partial.data_ptr<float>(), (int)grid.x,
+                     out.data_ptr<float>(), slot);
 }
 
 // standalone column sum for linear dbias: x [N, H] -> fp32 [H]
 torch::Tensor colsum(torch::Tensor x) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D [N, H]");
   long N = x.size(0);
   int H = x.size(1);
   TORCH_CHECK(H % 4 == 0, "H must be divisible by 4");
@@ -333,10 +381,25 @@ torch::Tensor colsum(torch::Tensor x) {
 void adamw_flat(torch::Tensor master, torch::Tensor grad, torch::Tensor m,
                 torch::Tensor v, torch::Tensor model, double lr, double beta1,
                 double beta2, double eps, double wd, long step) {
-  TORCH_CHECK(master.is_cuda() && master.scalar_type() == torch::kFloat);
+  TORCH_CHECK(master.is_cuda(), "master must be a GPU tensor");
+  fleetx::check_aux(master, torch::kFloat, master, "master");
   long n = master.numel();
-  TORCH_CHECK(n % 4 == 0);
+  TORCH_CHECK(n % 4 == 0, "master.numel() must be divisible by 4");
+  fleetx::check_data(grad, "grad");
+  TORCH_CHECK(grad.device() == master.device(), "grad is on ", grad.device(),
+              ", expected ", master.device());
+  fleetx::check_numel(grad, n, "grad");
+  fleetx::check_aux(m, torch::kFloat, master, "m");
+  fleetx::check_numel(m, n, "m");
+  fleetx::check_aux(v, torch::kFloat, master, "v");
+  fleetx::check_numel(v, n, "v");
   bool has_model = model.defined() && model.numel() > 0;
+  if (has_model) {
+    fleetx::check_data(model, "model");
+    TORCH_CHECK(model.device() == master.device(), "model is on ",
+                model.device(), ", expected ", master.device());
+    fleetx::check_numel(model, n, "model");
+  }
   float bc1 = 1.f - powf((float)beta1, (float)step);
   float bc2 = 1.f - powf((float)beta2, (float)step);
   auto stream = at::hip::getCurrentHIPStream();
@@ -359,8 +422,16 @@ void adamw_flat(torch::Tensor master, torch::Tensor grad, torch::Tensor m,
 }
 
 torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cos, torch::Tensor sin) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4);
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() == 4, "x must be 4-D [B, H, S, D]");
   int S = x.size(2), D = x.size(3);
+  TORCH_CHECK(D % 2 == 0, "head dim must be even, got ", D);
+  fleetx::check_aux(cos, torch::kFloat, x, "cos");
+  fleetx::check_aux(sin, torch::kFloat, x, "sin");
+  TORCH_CHECK(cos.dim() == 2 && cos.size(0) == S && cos.size(1) == D / 2,
+              "cos must be [S, D/2]");
+  TORCH_CHECK(sin.dim() == 2 && sin.size(0) == S && sin.size(1) == D / 2,
+              "sin must be [S, D/2]");
   long rows = x.numel() / D;
   auto y = torch::empty_like(x);
   auto stream = at::hip::getCurrentHIPStream();

@@ -6,8 +6,9 @@
 //   bwd: dx = ln_bwd(dy) (+ dsum)   — the residual-stream gradient join
 // One 256-thread block per row (grid-stride); compile-time (VEC, ITERS)
 // covers the transformer hidden sizes (1024/2048/4096/5120/8192); a
-// generic two-pass kernel backstops any other H.
+// generic kernel that re-reads the row backstops any other H.
 #include "common.h"
+#include "tensor_checks.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -116,7 +117,21 @@ __global__ __launch_bounds__(BLOCK) void ln_fwd_reg_kernel(
     __syncthreads();
     ss = block_reduce_sum<BLOCK>(ss, sred);
     float mu = rms ? 0.f : s / H;
-    float var = ss / H - mu * mu;
+    float ex2 = ss / H;
+    float var = ex2 - mu * mu;
+    // two-pass where E[x^2] - mu^2 cancels (mu^2 > 3 var, or var <= 0 / NaN):
+    // the one-pass error is ~2^-24 * E[x^2] / var, harmless below that
+    if (!rms && !(var >= 0.25f * ex2)) {  // block-uniform
+      float sd = 0.f;
+#pragma unroll
+      for (int it = 0; it < ITERS; ++it)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          float d = v[it][j] - mu;
+          sd += d * d;
+        }
+      var = block_reduce_sum<BLOCK>(sd, sred) / H;
+    }
     float rs = rsqrtf(var + eps);
     if (threadIdx.x == 0) {
       if (!rms && mean) mean[row] = mu;
@@ -136,7 +151,8 @@ __global__ __launch_bounds__(BLOCK) void ln_fwd_reg_kernel(
   }
 }
 
-// generic fallback (two passes over x, any H % 4 == 0)
+// generic fallback (two passes over x, a third where the variance needs it;
+// any H % 4 == 0)
 template <typename T, int VEC>
 __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
                               const T* __restrict__ w,
@@ -169,13 +185,31 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res
     __syncthreads();
     ss = block_reduce_sum<BLOCK>(ss, sred);
     float mu = rms ? 0.f : s / H;
-    float var = ss / H - mu * mu;
+    float ex2 = ss / H;
+    float var = ex2 - mu * mu;
+    // each thread re-reads only the elements it stored itself, so the
+    // rounded sum is visible without a fence
+    const T* sr = res ? sum_out + (long)row * H : xr;
+    // two-pass where E[x^2] - mu^2 cancels (mu^2 > 3 var, or var <= 0 / NaN):
+    // the one-pass error is ~2^-24 * E[x^2] / var, harmless below that
+    if (!rms && !(var >= 0.25f * ex2)) {  // block-uniform
+      float sd = 0.f;
+      for (int i = threadIdx.x * VEC; i < H; i += BLOCK * VEC) {
+        float v[VEC];
+        load_vec<T, VEC>(sr + i, v);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          float d = v[j] - mu;
+          sd += d * d;
+        }
+      }
+      var = block_reduce_sum<BLOCK>(sd, sred) / H;
+    }
     float rs = rsqrtf(var + eps);
     if (threadIdx.x == 0) {
       if (!rms && mean) mean[row] = mu;
       rstd[row] = rs;
     }
-    const T* sr = res ? sum_out + (long)row * H : xr;
     T* yr = y + (long)row * H;
     for (int i = threadIdx.x * VEC; i < H; i += BLOCK * VEC) {
       float v[VEC], wv[VEC], o[VEC];
@@ -404,13 +438,22 @@ static std::vector<torch::Tensor> ln_fwd_common(torch::Tensor x,
                                                 torch::Tensor w,
                                                 c10::optional<torch::Tensor> b,
                                                 double eps, bool rms) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D [N, H]");
   int N = x.size(0), H = x.size(1);
+  TORCH_CHECK(H % 4 == 0, "hidden size must be divisible by 4");
+  fleetx::check_same(w, x, "w");
+  fleetx::check_numel(w, H, "w");
+  if (b.has_value()) {
+    fleetx::check_same(*b, x, "b");
+    fleetx::check_numel(*b, H, "b");
+  }
   auto y = torch::empty_like(x);
   torch::Tensor sum_out;
   bool has_res = res.has_value();
   if (has_res) {
-    TORCH_CHECK(res->sizes() == x.sizes() && res->is_contiguous());
+    fleetx::check_same(*res, x, "res");
+    TORCH_CHECK(res->sizes() == x.sizes(), "res must have the shape of x");
     sum_out = torch::empty_like(x);
   }
   auto mean = rms ? torch::Tensor()
@@ -471,7 +514,24 @@ static std::vector<torch::Tensor> ln_bwd_impl(torch::Tensor dy, torch::Tensor x,
                                               torch::Tensor rstd,
                                               c10::optional<torch::Tensor> dsum,
                                               bool rms) {
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D [N, H]");
   int N = x.size(0), H = x.size(1);
+  TORCH_CHECK(H % 4 == 0, "hidden size must be divisible by 4");
+  fleetx::check_same(dy, x, "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "dy must have the shape of x");
+  fleetx::check_same(w, x, "w");
+  fleetx::check_numel(w, H, "w");
+  if (!rms) {
+    fleetx::check_aux(mean_or_empty, torch::kFloat, x, "mean");
+    fleetx::check_numel(mean_or_empty, N, "mean");
+  }
+  fleetx::check_aux(rstd, torch::kFloat, x, "rstd");
+  fleetx::check_numel(rstd, N, "rstd");
+  if (dsum.has_value()) {
+    fleetx::check_same(*dsum, x, "dsum");
+    TORCH_CHECK(dsum->sizes() == x.sizes(), "dsum must have the shape of x");
+  }
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({H}, x.options().dtype(torch::kFloat));
   auto db = rms ? torch::Tensor()

@@ -9,6 +9,7 @@
 // unstable — harmless: expert FFNs act row-wise and the combine uses the
 // inverse of the SAME permutation.
 #include "common.h"
+#include "tensor_checks.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -60,10 +61,12 @@ __global__ void moe_scatter_kernel(const long* __restrict__ expert_ids,
 std::vector<torch::Tensor> moe_dispatch(torch::Tensor x,
                                         torch::Tensor expert_ids,
                                         long num_experts, long top_k) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
-  TORCH_CHECK(expert_ids.scalar_type() == torch::kLong &&
-              expert_ids.is_contiguous());
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D [T, D]");
+  fleetx::check_aux(expert_ids, torch::kLong, x, "expert_ids");
+  TORCH_CHECK(num_experts >= 1 && top_k >= 1);
   long S = expert_ids.numel();
+  fleetx::check_numel(expert_ids, x.size(0) * top_k, "expert_ids");
   int D = x.size(1);
   TORCH_CHECK(D % 4 == 0, "d_model must be divisible by 4");
   auto stream = at::hip::getCurrentHIPStream();
@@ -94,7 +97,6 @@ std::vector<torch::Tensor> moe_dispatch(torch::Tensor x,
     if (D % 8 == 0) LAUNCH_SCATTER(__hip_bfloat16, 8);
     else LAUNCH_SCATTER(__hip_bfloat16, 4);
   } else {
-    TORCH_CHECK(x.scalar_type() == torch::kFloat);
     if (D % 8 == 0) LAUNCH_SCATTER(float, 8);
     else LAUNCH_SCATTER(float, 4);
   }

@@ -1,5 +1,6 @@
 // Fused scale+causal-mask+softmax and cross-entropy kernels, gfx950.
 #include "common.h"
+#include "tensor_checks.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -282,6 +283,7 @@ __global__ void vp_ce_bwd_kernel(const float* __restrict__ dloss,
 
 }  // namespace
 
+// `tensor` has passed fleetx::check_data: it is bf16 or fp32
 #define DISPATCH_T(tensor, ...)                         \
   if ((tensor).scalar_type() == torch::kBFloat16) {     \
     using T = __hip_bfloat16;                           \
@@ -292,7 +294,8 @@ __global__ void vp_ce_bwd_kernel(const float* __restrict__ dloss,
   }
 
 torch::Tensor softmax_causal_fwd(torch::Tensor s, double scale) {
-  TORCH_CHECK(s.is_cuda() && s.is_contiguous() && s.dim() == 4);
+  fleetx::check_data(s, "s");
+  TORCH_CHECK(s.dim() == 4, "s must be 4-D [B, H, Sq, Sk]");
   int Sq = s.size(2), Sk = s.size(3);
   long rows = s.numel() / Sk;
   auto y = torch::empty_like(s);
@@ -308,10 +311,18 @@ torch::Tensor softmax_causal_fwd(torch::Tensor s, double scale) {
 // with period `inner` / outer stride `outer` (see kernel comment)
 torch::Tensor softmax_bias_fwd(torch::Tensor s, torch::Tensor bias,
                                long inner, long outer, double scale) {
-  TORCH_CHECK(s.is_cuda() && s.is_contiguous() && bias.is_contiguous());
+  fleetx::check_data(s, "s");
+  fleetx::check_same(bias, s, "bias");
+  TORCH_CHECK(s.dim() >= 1 && bias.dim() >= 1);
   int K = s.size(-1);
-  TORCH_CHECK(bias.size(-1) == K);
+  TORCH_CHECK(bias.size(-1) == K, "bias and s differ in the last dim");
   long rows = s.numel() / K;
+  // the largest bias row the kernel forms must exist
+  TORCH_CHECK(inner >= 1 && outer >= inner && outer % inner == 0,
+              "bad bias period");
+  TORCH_CHECK(rows == 0 || ((rows - 1) / outer) * inner + inner <=
+                               bias.numel() / K,
+              "bias is too small for this period");
   auto y = torch::empty_like(s);
   auto stream = at::hip::getCurrentHIPStream();
   DISPATCH_T(s, hipLaunchKernelGGL((softmax_bias_fwd_kernel<T>), dim3(rows),
@@ -325,7 +336,9 @@ torch::Tensor softmax_bias_fwd(torch::Tensor s, torch::Tensor bias,
 
 torch::Tensor softmax_causal_bwd(torch::Tensor dy, torch::Tensor y,
                                  double scale) {
-  TORCH_CHECK(y.is_cuda() && y.is_contiguous() && dy.is_contiguous());
+  fleetx::check_data(y, "y");
+  fleetx::check_same(dy, y, "dy");
+  TORCH_CHECK(dy.sizes() == y.sizes(), "dy must have the shape of y");
   int Sk = y.size(-1);
   long rows = y.numel() / Sk;
   auto ds = torch::empty_like(y);
@@ -341,9 +354,12 @@ torch::Tensor softmax_causal_bwd(torch::Tensor dy, torch::Tensor y,
 std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
                                              torch::Tensor labels,
                                              long ignore_index) {
-  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous());
+  fleetx::check_data(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be 2-D [N, V]");
   long N = logits.size(0);
   int V = logits.size(1);
+  fleetx::check_aux(labels, torch::kLong, logits, "labels");
+  fleetx::check_numel(labels, N, "labels");
   auto loss = torch::empty({N}, logits.options().dtype(torch::kFloat));
   auto lse = torch::empty({N}, logits.options().dtype(torch::kFloat));
   auto stream = at::hip::getCurrentHIPStream();
@@ -360,10 +376,18 @@ std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
 torch::Tensor cross_entropy_bwd(torch::Tensor dloss, torch::Tensor logits,
                                 torch::Tensor labels, torch::Tensor lse,
                                 long ignore_index) {
+  fleetx::check_data(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be 2-D [N, V]");
   long N = logits.size(0);
   int V = logits.size(1);
+  fleetx::check_aux(dloss, torch::kFloat, logits, "dloss");
+  fleetx::check_numel(dloss, N, "dloss");
+  fleetx::check_aux(labels, torch::kLong, logits, "labels");
+  fleetx::check_numel(labels, N, "labels");
+  fleetx::check_aux(lse, torch::kFloat, logits, "lse");
+  fleetx::check_numel(lse, N, "lse");
   auto dl = torch::empty_like(logits);
-  auto dlf = dloss.to(torch::kFloat).contiguous();
+  const auto& dlf = dloss;
   auto stream = at::hip::getCurrentHIPStream();
   DISPATCH_T(logits, hipLaunchKernelGGL((ce_bwd_kernel<T>), dim3(N),
                                         dim3(BLOCK), 0, stream,
@@ -376,6 +400,8 @@ torch::Tensor cross_entropy_bwd(torch::Tensor dloss, torch::Tensor logits,
 }
 
 torch::Tensor row_max(torch::Tensor x) {
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D [N, V]");
   long N = x.size(0);
   int V = x.size(1);
   auto out = torch::empty({N}, x.options().dtype(torch::kFloat));
@@ -387,7 +413,11 @@ torch::Tensor row_max(torch::Tensor x) {
 }
 
 torch::Tensor row_sumexp(torch::Tensor x, torch::Tensor gmax) {
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D [N, V]");
   long N = x.size(0);
+  fleetx::check_aux(gmax, torch::kFloat, x, "gmax");
+  fleetx::check_numel(gmax, N, "gmax");
   int V = x.size(1);
   auto out = torch::empty({N}, x.options().dtype(torch::kFloat));
   auto stream = at::hip::getCurrentHIPStream();
@@ -400,7 +430,11 @@ torch::Tensor row_sumexp(torch::Tensor x, torch::Tensor gmax) {
 
 torch::Tensor gather_label_logit(torch::Tensor x, torch::Tensor labels,
                                  long start, long ignore_index) {
+  fleetx::check_data(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D [N, V]");
   long N = x.size(0);
+  fleetx::check_aux(labels, torch::kLong, x, "labels");
+  fleetx::check_numel(labels, N, "labels");
   int V = x.size(1);
   auto out = torch::empty({N}, x.options().dtype(torch::kFloat));
   auto stream = at::hip::getCurrentHIPStream();
@@ -417,10 +451,18 @@ torch::Tensor gather_label_logit(torch::Tensor x, torch::Tensor labels,
 torch::Tensor vp_ce_bwd(torch::Tensor dloss, torch::Tensor logits,
                         torch::Tensor labels, torch::Tensor lse, long start,
                         long ignore_index) {
+  fleetx::check_data(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be 2-D [N, V]");
   long N = logits.size(0);
   int V = logits.size(1);
+  fleetx::check_aux(dloss, torch::kFloat, logits, "dloss");
+  fleetx::check_numel(dloss, N, "dloss");
+  fleetx::check_aux(labels, torch::kLong, logits, "labels");
+  fleetx::check_numel(labels, N, "labels");
+  fleetx::check_aux(lse, torch::kFloat, logits, "lse");
+  fleetx::check_numel(lse, N, "lse");
   auto dl = torch::empty_like(logits);
-  auto dlf = dloss.to(torch::kFloat).contiguous();
+  const auto& dlf = dloss;
   auto stream = at::hip::getCurrentHIPStream();
   DISPATCH_T(logits, hipLaunchKernelGGL((vp_ce_bwd_kernel<T>), dim3(N),
                                         dim3(BLOCK), 0, stream,

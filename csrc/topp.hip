@@ -5,6 +5,7 @@
 // torch.sort on the wrapper side; this kernel does the block-wide
 // inclusive scan over sorted probs, the nucleus cutoff, and the draw.
 #include "common.h"
+#include "tensor_checks.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -94,10 +95,19 @@ __global__ void topp_select_kernel(const float* __restrict__ sorted_p,
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
                                        torch::Tensor top_p, torch::Tensor u) {
-  TORCH_CHECK(sorted_p.is_cuda() && sorted_p.dim() == 2 &&
-              sorted_p.scalar_type() == torch::kFloat);
+  TORCH_CHECK(sorted_p.is_cuda(), "sorted_p must be a GPU tensor");
+  fleetx::check_aux(sorted_p, torch::kFloat, sorted_p, "sorted_p");
+  TORCH_CHECK(sorted_p.dim() == 2, "sorted_p must be 2-D [B, V]");
   long B = sorted_p.size(0);
   int V = sorted_p.size(1);
+  TORCH_CHECK(V >= 1, "sorted_p must have at least one column");
+  fleetx::check_aux(sorted_idx, torch::kLong, sorted_p, "sorted_idx");
+  TORCH_CHECK(sorted_idx.sizes() == sorted_p.sizes(),
+              "sorted_idx must have the shape of sorted_p");
+  fleetx::check_aux(top_p, torch::kFloat, sorted_p, "top_p");
+  fleetx::check_numel(top_p, B, "top_p");
+  fleetx::check_aux(u, torch::kFloat, sorted_p, "u");
+  fleetx::check_numel(u, B, "u");
   auto out_id = torch::empty({B, 1}, sorted_p.options().dtype(torch::kLong));
   auto out_p = torch::empty({B, 1}, sorted_p.options());
   auto stream = at::hip::getCurrentHIPStream();

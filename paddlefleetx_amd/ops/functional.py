@@ -33,11 +33,20 @@ __all__ = [
 # LayerNorm / RMSNorm
 # ---------------------------------------------------------------------------
 
+def _as_dtype(p, dtype):
+    """Parameters (fp32 by default) follow the activation dtype: the
+    kernels read every operand with the element type of x."""
+    return p if p is None or p.dtype == dtype else p.to(dtype)
+
+
 class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
         shape = x.shape
         x2 = x.contiguous().view(-1, shape[-1])
+        ctx.param_dtype = weight.dtype
+        weight = _as_dtype(weight, x2.dtype)
+        bias = _as_dtype(bias, x2.dtype)
         if use_hip(x2):
             y, mean, rstd = hip_ext().layernorm_fwd(x2, weight, bias, eps)
         else:
@@ -53,7 +62,8 @@ class _LayerNormFn(torch.autograd.Function):
             dx, dw, db = hip_ext().layernorm_bwd(dy2, x2, weight, mean, rstd)
         else:
             dx, dw, db = ref.layernorm_bwd(dy2, x2, weight, mean, rstd)
-        return dx.view(dy.shape), dw.to(weight.dtype), db.to(weight.dtype), None
+        return (dx.view(dy.shape), dw.to(ctx.param_dtype),
+                db.to(ctx.param_dtype), None)
 
 
 def layernorm(x, weight, bias, eps: float = 1e-5):
@@ -71,6 +81,9 @@ class _LayerNormResidualFn(torch.autograd.Function):
         shape = x.shape
         x2 = x.contiguous().view(-1, shape[-1])
         r2 = res.contiguous().view(-1, shape[-1])
+        ctx.param_dtype = weight.dtype
+        weight = _as_dtype(weight, x2.dtype)
+        bias = _as_dtype(bias, x2.dtype)
         if use_hip(x2):
             y, mean, rstd, s = hip_ext().layernorm_fwd_residual(
                 x2, r2, weight, bias, eps)
@@ -100,7 +113,8 @@ class _LayerNormResidualFn(torch.autograd.Function):
                 dx, dw, db = ref.layernorm_bwd(dy2, s2, weight, mean, rstd)
         dxv = dx.view(dy.shape)
         # d(x) = d(res) = dx (s = x + res is linear in both)
-        return dxv, dxv, dw.to(weight.dtype), db.to(weight.dtype), None
+        return (dxv, dxv, dw.to(ctx.param_dtype), db.to(ctx.param_dtype),
+                None)
 
 
 def layernorm_residual(x, res, weight, bias, eps: float = 1e-5):
@@ -113,6 +127,8 @@ class _RMSNormFn(torch.autograd.Function):
     def forward(ctx, x, weight, eps):
         shape = x.shape
         x2 = x.contiguous().view(-1, shape[-1])
+        ctx.param_dtype = weight.dtype
+        weight = _as_dtype(weight, x2.dtype)
         if use_hip(x2):
             y, rstd = hip_ext().rmsnorm_fwd(x2, weight, eps)
         else:
@@ -128,7 +144,7 @@ class _RMSNormFn(torch.autograd.Function):
             dx, dw = hip_ext().rmsnorm_bwd(dy2, x2, weight, rstd)
         else:
             dx, dw = ref.rmsnorm_bwd(dy2, x2, weight, rstd)
-        return dx.view(dy.shape), dw.to(weight.dtype), None
+        return dx.view(dy.shape), dw.to(ctx.param_dtype), None
 
 
 def rmsnorm(x, weight, eps: float = 1e-6):
@@ -166,14 +182,19 @@ class _BiasGeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias):
         xc = x.contiguous()
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        bias = _as_dtype(bias, xc.dtype)
         if use_hip(xc):
             y = hip_ext().bias_gelu_fwd(xc.view(-1, xc.shape[-1]),
                                         bias if bias is not None else torch.Tensor())
             y = y.view(xc.shape)
         else:
             y = ref.bias_gelu_fwd(xc, bias)
-        ctx.save_for_backward(xc, bias if bias is not None else None)
         ctx.has_bias = bias is not None
+        if ctx.has_bias:
+            ctx.save_for_backward(xc, bias)
+        else:
+            ctx.save_for_backward(xc)
         return y
 
     @staticmethod
@@ -193,7 +214,7 @@ class _BiasGeluFn(torch.autograd.Function):
         else:
             dx, db = ref.bias_gelu_bwd(dyc, x, bias)
         if db is not None and bias is not None:
-            db = db.to(bias.dtype)
+            db = db.to(ctx.bias_dtype)
         return dx, db
 
 
@@ -451,7 +472,8 @@ class _SoftmaxBiasFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores, bias, scale, period):
         sc = scores.contiguous()
-        bc_ = bias.contiguous()
+        bc_ = _as_dtype(bias, sc.dtype).contiguous()
+        ctx.bias_dtype = bias.dtype
         y = hip_ext().softmax_bias_fwd(sc, bc_, period[0], period[1], scale)
         ctx.save_for_backward(y)
         ctx.scale = scale
@@ -467,7 +489,7 @@ class _SoftmaxBiasFn(torch.autograd.Function):
         red = [i for i, (a, b) in enumerate(zip(y.shape, ctx.bias_shape))
                if b == 1 and a != 1]
         db = dlogits.sum(dim=red, keepdim=True) if red else dlogits
-        return ds, db.to(y.dtype), None, None
+        return ds, db.to(ctx.bias_dtype), None, None
 
 
 def fused_softmax_bias(scores, bias, scale: float = 1.0):
@@ -490,6 +512,7 @@ class _CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ignore_index):
         lc = logits.contiguous()
+        labels = labels.contiguous()
         if use_hip(lc):
             loss, lse = hip_ext().cross_entropy_fwd(lc, labels, ignore_index)
         else:
@@ -502,8 +525,9 @@ class _CrossEntropyFn(torch.autograd.Function):
     def backward(ctx, dloss):
         logits, labels, lse = ctx.saved_tensors
         if use_hip(logits):
-            dl = hip_ext().cross_entropy_bwd(dloss.contiguous(), logits, labels,
-                                             lse, ctx.ignore_index)
+            dl = hip_ext().cross_entropy_bwd(dloss.float().contiguous(),
+                                             logits, labels, lse,
+                                             ctx.ignore_index)
         else:
             dl = ref.cross_entropy_bwd(dloss, logits, labels, lse, ctx.ignore_index)
         return dl, None, None
@@ -541,6 +565,7 @@ class _RopeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cos, sin):
         xc = x.contiguous()
+        cos, sin = cos.float().contiguous(), sin.float().contiguous()
         if use_hip(xc):
             y = hip_ext().rope_fwd(xc, cos, sin)
         else:

@@ -240,6 +240,7 @@ class _VocabParallelCE(torch.autograd.Function):
             from paddlefleetx_amd.ops import hip_ext
             ext = hip_ext()
             lc = logits.contiguous()
+            labels = labels.contiguous()
             lmax = ext.row_max(lc)
             if group is not None:
                 dist.all_reduce(lmax, op=dist.ReduceOp.MAX, group=group)
@@ -281,8 +282,9 @@ class _VocabParallelCE(torch.autograd.Function):
         logits, labels, lse = ctx.saved_tensors
         if logits.is_cuda:
             from paddlefleetx_amd.ops import hip_ext
-            g = hip_ext().vp_ce_bwd(dloss.contiguous(), logits, labels, lse,
-                                    ctx.vocab_start, ctx.ignore_index)
+            g = hip_ext().vp_ce_bwd(dloss.float().contiguous(), logits,
+                                    labels, lse, ctx.vocab_start,
+                                    ctx.ignore_index)
             return g, None, None, None, None, None
         lf = logits.float()
         p = torch.exp(lf - lse[:, None])
