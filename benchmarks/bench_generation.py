@@ -6,7 +6,8 @@ Counterpart of the reference's inference latency harness
 
     python benchmarks/bench_generation.py [--model GPT-1.3B] \
         [--prompt-len 128] [--gen-len 64] \
-        [--static-cache [--kv-dtype fp8] [--fused-sampling [--capture]]]
+        [--static-cache [--kv-dtype fp8] [--fused-sampling [--capture]] \
+         [--fused-linear]]
 """
 
 import argparse
@@ -46,6 +47,10 @@ def main():
     p.add_argument("--capture", action="store_true",
                    help="replay a captured decode step per token "
                         "(Generation.capture_decode); needs --fused-sampling")
+    p.add_argument("--fused-linear", action="store_true",
+                   help="decode-step linears and logits through "
+                        "ops.decode_linear (Generation.fused_decode_linear); "
+                        "needs --static-cache")
     p.add_argument("--finish-check-interval", type=int, default=None,
                    help="Generation.finish_check_interval (fused sampling)")
     p.add_argument("--fixed-capacity", action="store_true",
@@ -57,6 +62,8 @@ def main():
         p.error("--capture needs --fused-sampling")
     if args.fused_sampling and not args.static_cache:
         p.error("--fused-sampling needs --static-cache")
+    if args.fused_linear and not args.static_cache:
+        p.error("--fused-linear needs --static-cache")
 
     from paddlefleetx_amd.parallel.env import set_hcg
     from paddlefleetx_amd.parallel.topology import HybridTopology
@@ -85,6 +92,7 @@ def main():
             "kv_cache_dtype": args.kv_dtype,
             "fused_sampling": args.fused_sampling,
             "capture_decode": args.capture,
+            "fused_decode_linear": args.fused_linear,
             **({"finish_check_interval": args.finish_check_interval}
                if args.finish_check_interval else {}),
             **({"kv_cache_capacity": args.prompt_len + args.gen_len}
@@ -96,6 +104,7 @@ def main():
           f"gen={args.gen_len} top_p={args.top_p} "
           f"static_cache={args.static_cache} kv_dtype={args.kv_dtype} "
           f"fused_sampling={args.fused_sampling} capture={args.capture} "
+          f"fused_linear={args.fused_linear} "
           f"({dev})")
     for bs in [int(b) for b in args.batches.split(",")]:
         ids = torch.randint(0, vocab - 2, (bs, args.prompt_len), device=dev)

@@ -1,6 +1,7 @@
 // Torch extension bindings for the gfx950 fused-op kernels.
 #include <torch/extension.h>
 
+#include <string>
 #include <vector>
 
 // layernorm.hip
@@ -81,6 +82,12 @@ torch::Tensor decode_attn_fp8(torch::Tensor qkv, torch::Tensor k_cache,
 void kv_store_fp8(torch::Tensor qkv, torch::Tensor k_cache,
                   torch::Tensor v_cache, torch::Tensor k_scale,
                   torch::Tensor v_scale);
+// decode_linear.hip
+torch::Tensor decode_linear(torch::Tensor x, torch::Tensor weight,
+                            c10::optional<torch::Tensor> bias,
+                            c10::optional<torch::Tensor> residual,
+                            const std::string& act, long rows, long waves,
+                            long nontemporal);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -160,6 +167,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "positions [0,S) of an fp8 KV cache",
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("k_scale"), py::arg("v_scale"));
+  m.def("decode_linear", &decode_linear,
+        "y = act(x W^T + bias) + residual for 1 <= M <= 16 bf16 rows: W "
+        "streamed once, epilogue fused (rows/waves/nontemporal: tuning "
+        "overrides, default automatic)",
+        py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
+        py::arg("residual") = py::none(), py::arg("act") = "none",
+        py::arg("rows") = 0, py::arg("waves") = 0,
+        py::arg("nontemporal") = -1);
   m.def("topp_select", &topp_select, "top-p nucleus cutoff + draw");
   m.def("sample_token", &sample_token,
         "logits row -> next token in one launch (min length, repetition "

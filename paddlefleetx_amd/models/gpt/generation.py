@@ -32,7 +32,7 @@ import torch.nn.functional as F
 
 from paddlefleetx_amd.models.gpt.model import GPTModel, StaticKVCache
 from paddlefleetx_amd.models.gpt.processor import get_logits_processor
-from paddlefleetx_amd.ops import sample_token, topp_sampling
+from paddlefleetx_amd.ops import decode_linear, sample_token, topp_sampling
 from paddlefleetx_amd.parallel.env import get_hcg
 from paddlefleetx_amd.parallel.tp import parallel_matmul
 from paddlefleetx_amd.utils.log import logger
@@ -121,6 +121,19 @@ class GPTForGeneration(nn.Module):
                            "true: staying eager")
             self.capture_decode = False
         self._graph_state = None
+        # every linear of a static-cache decode step (and the logits of the
+        # fused-sampling step) as one ops.decode_linear launch
+        self.fused_decode_linear = bool(cfg.get("fused_decode_linear", False))
+        if self.fused_decode_linear and not self.static_kv_cache:
+            raise ValueError(
+                "Generation.fused_decode_linear: true needs static_kv_cache: "
+                "true (the fused layer runs against a static cache slot)")
+        if self.fused_decode_linear and \
+                get_hcg().get_model_parallel_world_size() != 1:
+            logger.warning("Generation.fused_decode_linear needs "
+                           "model-parallel size 1: staying on the existing "
+                           "path")
+            self.fused_decode_linear = False
 
     # -- one forward --------------------------------------------------------
     def _logits(self, input_ids, position_ids, caches):
@@ -138,7 +151,8 @@ class GPTForGeneration(nn.Module):
                              attn.num_heads_local, max_len, attn.head_dim,
                              dtype=attn.qkv.weight.dtype, device=device,
                              kv_dtype=self.kv_cache_dtype,
-                             max_seq_len=max_seq_len)
+                             max_seq_len=max_seq_len,
+                             fused_decode_linear=self.fused_decode_linear)
 
     # -- fused sampling -----------------------------------------------------
     def _capacity(self, prompt_len: int) -> int:
@@ -168,9 +182,13 @@ class GPTForGeneration(nn.Module):
         pos = cache.lens.long().unsqueeze(1)
         hidden, _ = self.gpt(st["next_tokens"], pos, caches=cache,
                              use_cache=True)
-        logits = parallel_matmul(
-            hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight,
-            parallel_output=False)
+        if self.fused_decode_linear:
+            logits = decode_linear(
+                hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight)
+        else:
+            logits = parallel_matmul(
+                hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight,
+                parallel_output=False)
         sample_token(logits, st["ids_buf"], cache.lens, st["unfinished"],
                      st["u"], st["next_tokens"], **kw)
 

@@ -23,7 +23,8 @@ import torch.nn.functional as F
 from torch.utils.checkpoint import checkpoint
 
 from paddlefleetx_amd.ops import (FusedLayerNorm, bias_gelu,
-                                  decode_attention, flash_attention,
+                                  decode_attention, decode_linear,
+                                  flash_attention,
                                   flash_attention_packed,
                                   fused_softmax_causal, kv_cache_store_fp8)
 from paddlefleetx_amd.parallel.env import get_hcg
@@ -81,13 +82,18 @@ class StaticKVCache:
     kernel clamps per row, so this costs balance, not correctness; it makes
     the split choice independent of the step, which a captured decode step
     needs (and an eager run can share).
+
+    fused_decode_linear (Generation.fused_decode_linear): decoder layers
+    that decode one token against this cache run their linears through
+    ops.decode_linear (TransformerDecoderLayer._forward_decode_fused).
     """
 
     def __init__(self, num_layers: int, batch_size: int, num_heads: int,
                  max_len: int, head_dim: int,
                  dtype: Optional[torch.dtype] = None, device=None,
                  kv_dtype: Optional[str] = None,
-                 max_seq_len: Optional[int] = None):
+                 max_seq_len: Optional[int] = None,
+                 fused_decode_linear: bool = False):
         assert kv_dtype in (None, "bf16", "fp8"), \
             f"StaticKVCache: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}"
         self.kv_dtype = "fp8" if kv_dtype == "fp8" else "bf16"
@@ -95,6 +101,7 @@ class StaticKVCache:
         assert max_seq_len is None or 1 <= int(max_seq_len) <= self.capacity, \
             f"StaticKVCache: max_seq_len {max_seq_len} not in [1, {max_len}]"
         self.max_seq_len = None if max_seq_len is None else int(max_seq_len)
+        self.fused_decode_linear = bool(fused_decode_linear)
         shape = (batch_size, num_heads, self.capacity, head_dim)
         if self.kv_dtype == "fp8":
             dtype = torch.float8_e4m3fn
@@ -278,6 +285,22 @@ class MultiHeadAttention(nn.Module):
         out = self.out_proj(o)
         return out, new_cache
 
+    def _decode_core(self, qkv: torch.Tensor, slot: StaticKVSlot
+                     ) -> torch.Tensor:
+        """Decode attention of one new token (qkv [B, 1, 3H/mp]) against a
+        cache slot, before the output projection: [B, 1, H/mp]."""
+        B, S, _ = qkv.shape
+        assert S == 1
+        packed = qkv.view(B, S, self.num_heads_local, 3, self.head_dim)
+        n_cached = slot.owner.max_len
+        assert n_cached + S <= slot.owner.capacity, \
+            f"StaticKVCache overflow: {n_cached}+{S} > {slot.owner.capacity}"
+        return decode_attention(packed, slot.k, slot.v, slot.owner.lens,
+                                scale=self.scale,
+                                max_seq_len=slot.owner.max_seq_len
+                                or n_cached + 1,
+                                k_scale=slot.k_scale, v_scale=slot.v_scale)
+
     def _forward_static(self, qkv: torch.Tensor, slot: StaticKVSlot
                         ) -> Tuple[torch.Tensor, StaticKVSlot]:
         """Inference against a preallocated cache slot. Decode (S == 1) is
@@ -293,12 +316,7 @@ class MultiHeadAttention(nn.Module):
         assert n_cached + S <= slot.owner.capacity, \
             f"StaticKVCache overflow: {n_cached}+{S} > {slot.owner.capacity}"
         if S == 1:
-            o = decode_attention(packed, slot.k, slot.v, slot.owner.lens,
-                                 scale=self.scale,
-                                 max_seq_len=slot.owner.max_seq_len
-                                 or n_cached + 1,
-                                 k_scale=slot.k_scale, v_scale=slot.v_scale)
-            return self.out_proj(o), slot
+            return self.out_proj(self._decode_core(qkv, slot)), slot
         assert n_cached == 0, \
             "StaticKVCache prefill (S > 1) needs an empty cache"
         if slot.fp8:
@@ -416,7 +434,27 @@ class TransformerDecoderLayer(nn.Module):
     def _attn_branch_nocache(self, x):
         return self._attn_branch(x)[0]
 
+    def _forward_decode_fused(self, x, slot: StaticKVSlot):
+        """One decode token with every linear as a decode_linear launch
+        (bias, GELU and the residual adds ride in the epilogues): 7
+        launches plus the attention merge."""
+        attn, ffn = self.attn, self.ffn
+        h = self.ln1(x)
+        qkv = decode_linear(h, attn.qkv.weight, attn.qkv.bias)
+        o = attn._decode_core(qkv, slot)
+        y = decode_linear(o, attn.out_proj.weight, attn.out_proj.bias,
+                          residual=x)
+        h2 = self.ln2(y)
+        u = decode_linear(h2, ffn.up.weight, ffn.up_bias, activation="gelu")
+        return decode_linear(u, ffn.down.weight, ffn.down.bias, residual=y)
+
     def forward(self, x, cache: Optional[KVCache] = None, use_cache: bool = False):
+        if (isinstance(cache, StaticKVSlot)
+                and cache.owner.fused_decode_linear
+                and x.shape[1] == 1 and not self.training
+                and isinstance(self.ffn, FFN) and not self.sequence_parallel):
+            z = self._forward_decode_fused(x, cache)
+            return (z, cache) if use_cache else z
         if self.use_recompute and self.recompute_granularity == "full_attn" \
                 and self.training and not use_cache and torch.is_grad_enabled():
             a = checkpoint(self._attn_branch_nocache, x,

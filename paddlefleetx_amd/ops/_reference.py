@@ -102,6 +102,27 @@ def bias_gelu_bwd(dy: torch.Tensor, x: torch.Tensor, bias: Optional[torch.Tensor
     return dx.to(x.dtype), db
 
 
+def decode_linear(x: torch.Tensor, weight: torch.Tensor,
+                  bias: Optional[torch.Tensor] = None,
+                  residual: Optional[torch.Tensor] = None,
+                  activation: Optional[str] = None) -> torch.Tensor:
+    """y = act(x @ weight^T + bias) + residual in fp32, one cast to x.dtype.
+
+    x [..., K], weight [N, K], bias [N], residual [..., N]; activation None
+    or "gelu" (the tanh form of bias_gelu_fwd).
+    """
+    assert activation in (None, "none", "gelu"), activation
+    yf = torch.matmul(x.float(), weight.float().t())
+    if bias is not None:
+        yf = yf + bias.float()
+    if activation == "gelu":
+        yf = 0.5 * yf * (1.0 + torch.tanh(
+            0.7978845608028654 * (yf + 0.044715 * yf ** 3)))
+    if residual is not None:
+        yf = yf + residual.float()
+    return yf.to(x.dtype)
+
+
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                   causal: bool, scale: Optional[float] = None
                   ) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -22,7 +22,7 @@ from paddlefleetx_amd.ops import hip_ext, use_hip
 
 __all__ = [
     "layernorm", "layernorm_residual", "rmsnorm", "FusedLayerNorm",
-    "FusedRMSNorm", "bias_gelu",
+    "FusedRMSNorm", "bias_gelu", "decode_linear",
     "flash_attention", "flash_attention_packed", "fused_softmax_causal",
     "fused_softmax_bias", "cross_entropy",
     "fused_adamw_flat", "rope", "topp_sampling",
@@ -220,6 +220,73 @@ class _BiasGeluFn(torch.autograd.Function):
 
 def bias_gelu(x, bias=None):
     return _BiasGeluFn.apply(x, bias)
+
+
+# ---------------------------------------------------------------------------
+# Weight-streaming linear for the decode step (M <= 16 rows)
+# ---------------------------------------------------------------------------
+
+DECODE_LINEAR_MAX_M = 16
+
+
+def _decode_linear_fits(x2, weight, bias, residual) -> bool:
+    """The contract of the decode_linear kernel (csrc/decode_linear.hip);
+    straight-line, it runs on every call of the eager decode loop."""
+    if not (use_hip(x2) and x2.dtype == torch.bfloat16
+            and weight.dtype == torch.bfloat16 and weight.dim() == 2):
+        return False
+    M, K = x2.shape
+    N = weight.shape[0]
+    if not (1 <= M <= DECODE_LINEAR_MAX_M and K >= 32 and K % 32 == 0
+            and N >= 8 and N % 8 == 0 and weight.shape[1] == K):
+        return False
+    grad = torch.is_grad_enabled()
+    for t in (x2, weight, bias, residual):
+        if t is not None and (
+                t.dtype != torch.bfloat16 or t.device != x2.device
+                or not t.is_contiguous() or (grad and t.requires_grad)):
+            return False
+    return x2.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
+
+
+def decode_linear(x, weight, bias=None, residual=None,
+                  activation: Optional[str] = None):
+    """y = act(x @ weight^T + bias) + residual for the decode step
+    (inference only; no autograd through the kernel).
+
+    x [..., K] (leading dimensions are flattened to M rows), weight [N, K]
+    in the nn.Linear / embedding layout, bias [N], residual [..., N];
+    activation None or "gelu" (the tanh form of bias_gelu).
+
+    bf16 CUDA operands with 1 <= M <= 16, K % 32 == 0 and N % 8 == 0, all
+    contiguous on one device, run the HIP kernel (an error if the extension
+    is missing): the weight is streamed once, the sum is kept in fp32
+    through the epilogue and rounded to bf16 once. Every other case (CPU,
+    fp32, M > 16, other K or N, strided operands, a tensor that requires
+    grad with grad enabled) computes the same expression from library ops.
+    """
+    assert activation in (None, "none", "gelu"), \
+        f"decode_linear: activation must be None or 'gelu', got {activation!r}"
+    gelu = activation == "gelu"
+    K = x.shape[-1]
+    N = weight.shape[0]
+    x2 = x.reshape(-1, K)
+    res2 = residual.reshape(-1, N) if residual is not None else None
+    if _decode_linear_fits(x2, weight, bias, res2):
+        y = hip_ext().decode_linear(x2, weight, bias, res2,
+                                    "gelu" if gelu else "none")
+        return y.view(*x.shape[:-1], N)
+    y = torch.nn.functional.linear(x, weight.to(x.dtype))
+    if bias is None and not gelu and residual is None:
+        return y
+    yf = y.float()
+    if bias is not None:
+        yf = yf + bias.float()
+    if gelu:
+        yf = torch.nn.functional.gelu(yf, approximate="tanh")
+    if residual is not None:
+        yf = yf + residual.float()
+    return yf.to(x.dtype)
 
 
 # ---------------------------------------------------------------------------
