@@ -6,6 +6,7 @@ then `+ bias`, bias_gelu or the residual add as separate launches).
 
     python benchmarks/bench_decode_linear.py [--iters 50] [--reps 5]
     python benchmarks/bench_decode_linear.py --sweep   # kernel variants
+    python benchmarks/bench_decode_linear.py --weight-dtype fp8 [--sweep]
 
 Shapes: the four GPT-1.3B layer linears and the tied logits matrix
 (N 50304, K 2048), each at M = 1, 4 and 16. Device-event timing around one
@@ -19,6 +20,12 @@ Infinity Cache (the footprint is printed). Needs a GPU: no CPU fallback.
 --sweep times the kernel's tuning overrides (rows per workgroup, waves per
 workgroup, non-temporal weight loads) against each other, alternating in the
 same way; it is how the automatic choice in decode_linear.hip was made.
+
+--weight-dtype fp8 times the fp8-weight kernel (csrc/decode_linear_fp8.hip:
+e4m3 codes, one fp32 scale per output row) against the bf16 decode_linear on
+the same shapes, the two alternating in one process; its bytes are N*K + 4*N.
+With --sweep it sweeps the fp8 kernel's variants instead. --model 6.7B takes
+the GPT-6.7B shapes (hidden 4096).
 """
 
 import argparse
@@ -32,12 +39,15 @@ import torch
 import torch.nn.functional as F
 
 HBM_MEASURED_TBS = 6.29  # MI355X measured HBM read rate (TB/s)
-H = 2048
-# name, N, K, epilogue of the decoder layer
-LAYER = [("qkv", 3 * H, H, "bias"), ("out_proj", H, H, "bias_res"),
-         ("ffn_up", 4 * H, H, "bias_gelu"), ("ffn_down", H, 4 * H, "bias_res"),
-         ("logits", 50304, H, "none")]
+HIDDEN = {"1.3B": 2048, "6.7B": 4096}
 MS = (1, 4, 16)
+
+
+def layer_shapes(H):
+    """name, N, K, epilogue of the decoder layer's linears and the logits."""
+    return [("qkv", 3 * H, H, "bias"), ("out_proj", H, H, "bias_res"),
+            ("ffn_up", 4 * H, H, "bias_gelu"),
+            ("ffn_down", H, 4 * H, "bias_res"), ("logits", 50304, H, "none")]
 
 
 def num_sets(nbytes, max_sets):
@@ -98,6 +108,12 @@ def main():
                         "host's launch rate (about 9 us per launch)")
     p.add_argument("--sweep", action="store_true",
                    help="time the kernel's (rows, waves, nt) variants")
+    p.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+                   help="fp8: the fp8-weight kernel against the bf16 one")
+    p.add_argument("--model", choices=sorted(HIDDEN), default="1.3B")
+    p.add_argument("--ms", type=int, nargs="+", default=list(MS))
+    p.add_argument("--only", nargs="+", default=None,
+                   help="names of the linears to run (default all)")
     args = p.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_decode_linear: no GPU present (no CPU fallback)")
@@ -112,17 +128,24 @@ def main():
           f"{'eager launches' if args.eager_launch else 'captured'}; "
           f"bytes = N*K*2; share = of "
           f"{HBM_MEASURED_TBS} TB/s measured HBM")
+    fp8 = args.weight_dtype == "fp8"
+    shapes = [sh for sh in layer_shapes(HIDDEN[args.model])
+              if args.only is None or sh[0] in args.only]
+    if fp8:
+        from paddlefleetx_amd.ops import _reference as ref
+        bench_fp8(ext, ref, decode_linear, shapes, dev, args)
+        return
     if not args.sweep:
         print(f"{'linear':>9} {'N':>6} {'K':>5} {'M':>3} {'MiB':>7} | "
               f"{'fused us':>9} {'TB/s':>6} {'share':>6} | "
               f"{'eager us':>9} {'TB/s':>6} {'share':>6} | speedup")
-    for name, N, K, ep in LAYER:
+    for name, N, K, ep in shapes:
         nbytes = N * K * 2
         nsets = num_sets(nbytes, args.max_sets)
         ws = [(torch.randn(N, K, device=dev) * 0.02).to(bf16)
               for _ in range(nsets)]
         bias = torch.randn(N, device=dev).to(bf16)
-        for M in MS:
+        for M in args.ms:
             x = torch.randn(M, K, device=dev).to(bf16)
             res = torch.randn(M, N, device=dev).to(bf16)
             b = None if ep == "none" else bias
@@ -183,6 +206,78 @@ def sweep(ext, name, N, K, M, x, ws, b, r, act, nbytes, args):
     print(f"{name:>9} N={N} K={K} M={M}: auto={med[-1]:.2f} us "
           f"({nbytes / med[-1] / 1e6:.2f} TB/s); best rows/waves/nt="
           f"{variants[best]} {med[best]:.2f} us | {cells}")
+
+
+FP8_VARIANTS = [(rows, waves, nt) for rows in (8, 16, 32, 64)
+                for waves in (4, 8) for nt in (0, 1)]
+
+
+def bench_fp8(ext, ref, decode_linear, shapes, dev, args):
+    """fp8 weights against bf16 weights, one weight set = (bf16 W, codes,
+    scales); both kernels rotate over the same number of sets, sized so the
+    SMALLER (fp8) footprint still exceeds the Infinity Cache."""
+    bf16 = torch.bfloat16
+    if not args.sweep:
+        print(f"{'linear':>9} {'N':>6} {'K':>5} {'M':>3} | "
+              f"{'fp8 us':>8} {'TB/s':>6} {'share':>6} | "
+              f"{'bf16 us':>8} {'TB/s':>6} {'share':>6} | bf16/fp8")
+    for name, N, K, ep in shapes:
+        nb8, nb16 = N * K + 4 * N, N * K * 2
+        nsets = num_sets(nb8, args.max_sets)
+        sets = []
+        for _ in range(nsets):
+            w = (torch.randn(N, K, device=dev) * 0.02).to(bf16)
+            codes, scale = ref.quantize_weight_rows(w)
+            sets.append((w, codes, scale))
+        bias = torch.randn(N, device=dev).to(bf16)
+        for M in args.ms:
+            x = torch.randn(M, K, device=dev).to(bf16)
+            res = torch.randn(M, N, device=dev).to(bf16)
+            b = None if ep == "none" else bias
+            r = res if ep == "bias_res" else None
+            act = "gelu" if ep == "bias_gelu" else None
+
+            def run8(s):
+                return decode_linear(x, s[1], b, r, act, weight_scale=s[2])
+
+            def run16(s):
+                return decode_linear(x, s[0], b, r, act)
+
+            with torch.no_grad():
+                want = ref.decode_linear_fp8(x, sets[0][1], sets[0][2], b, r,
+                                             act).float()
+                err = (run8(sets[0]).float() - want).abs().max().item()
+                # two bf16 ulps of the largest value
+                assert err <= 2.0 ** -6 * want.abs().max().item(), \
+                    f"fp8 kernel and twin disagree: {err}"
+                if args.sweep:
+                    a = act or "none"
+                    fns = [(lambda s, v=v: ext.decode_linear_fp8(
+                        x, s[1], s[2], b, r, a, *v)) for v in FP8_VARIANTS]
+                    fns.append(lambda s: ext.decode_linear_fp8(
+                        x, s[1], s[2], b, r, a))
+                    med, _ = alternate(fns, sets, args.iters, args.reps,
+                                       not args.eager_launch)
+                    best = min(range(len(FP8_VARIANTS)), key=lambda i: med[i])
+                    cells = " ".join(f"{v[0]}/{v[1]}/{v[2]}={u:.2f}"
+                                     for v, u in zip(FP8_VARIANTS, med))
+                    print(f"{name:>9} N={N} K={K} M={M}: auto={med[-1]:.2f} us"
+                          f" ({nb8 / med[-1] / 1e6:.2f} TB/s); best "
+                          f"rows/waves/nt={FP8_VARIANTS[best]} "
+                          f"{med[best]:.2f} us | {cells}", flush=True)
+                    continue
+                (u8, u16), (t8, t16) = alternate(
+                    (run8, run16), sets, args.iters, args.reps,
+                    not args.eager_launch)
+            g8, g16 = nb8 / u8 / 1e6, nb16 / u16 / 1e6  # TB/s
+            print(f"{name:>9} {N:6d} {K:5d} {M:3d} | "
+                  f"{u8:8.2f} {g8:6.2f} {100 * g8 / HBM_MEASURED_TBS:5.1f}% | "
+                  f"{u16:8.2f} {g16:6.2f} "
+                  f"{100 * g16 / HBM_MEASURED_TBS:5.1f}% | "
+                  f"{u16 / u8:5.2f}x  (fp8 min/max {min(t8):.2f}/"
+                  f"{max(t8):.2f}, bf16 {min(t16):.2f}/{max(t16):.2f}; "
+                  f"worst pairing {min(t16) / max(t8):.2f}x)", flush=True)
+        del sets
 
 
 if __name__ == "__main__":

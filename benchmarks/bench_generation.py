@@ -7,7 +7,7 @@ Counterpart of the reference's inference latency harness
     python benchmarks/bench_generation.py [--model GPT-1.3B] \
         [--prompt-len 128] [--gen-len 64] \
         [--static-cache [--kv-dtype fp8] [--fused-sampling [--capture]] \
-         [--fused-linear]]
+         [--fused-linear [--weight-dtype fp8]]]
 """
 
 import argparse
@@ -51,6 +51,10 @@ def main():
                    help="decode-step linears and logits through "
                         "ops.decode_linear (Generation.fused_decode_linear); "
                         "needs --static-cache")
+    p.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+                   help="storage of the weights the fused decode linears "
+                        "stream (Generation.decode_weight_dtype); fp8 needs "
+                        "--fused-linear")
     p.add_argument("--finish-check-interval", type=int, default=None,
                    help="Generation.finish_check_interval (fused sampling)")
     p.add_argument("--fixed-capacity", action="store_true",
@@ -64,6 +68,8 @@ def main():
         p.error("--fused-sampling needs --static-cache")
     if args.fused_linear and not args.static_cache:
         p.error("--fused-linear needs --static-cache")
+    if args.weight_dtype == "fp8" and not args.fused_linear:
+        p.error("--weight-dtype fp8 needs --fused-linear")
 
     from paddlefleetx_amd.parallel.env import set_hcg
     from paddlefleetx_amd.parallel.topology import HybridTopology
@@ -93,6 +99,7 @@ def main():
             "fused_sampling": args.fused_sampling,
             "capture_decode": args.capture,
             "fused_decode_linear": args.fused_linear,
+            "decode_weight_dtype": args.weight_dtype,
             **({"finish_check_interval": args.finish_check_interval}
                if args.finish_check_interval else {}),
             **({"kv_cache_capacity": args.prompt_len + args.gen_len}
@@ -105,6 +112,7 @@ def main():
           f"static_cache={args.static_cache} kv_dtype={args.kv_dtype} "
           f"fused_sampling={args.fused_sampling} capture={args.capture} "
           f"fused_linear={args.fused_linear} "
+          f"weight_dtype={args.weight_dtype} "
           f"({dev})")
     for bs in [int(b) for b in args.batches.split(",")]:
         ids = torch.randint(0, vocab - 2, (bs, args.prompt_len), device=dev)

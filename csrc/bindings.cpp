@@ -88,6 +88,13 @@ torch::Tensor decode_linear(torch::Tensor x, torch::Tensor weight,
                             c10::optional<torch::Tensor> residual,
                             const std::string& act, long rows, long waves,
                             long nontemporal);
+// decode_linear_fp8.hip
+torch::Tensor decode_linear_fp8(torch::Tensor x, torch::Tensor wq,
+                                torch::Tensor w_scale,
+                                c10::optional<torch::Tensor> bias,
+                                c10::optional<torch::Tensor> residual,
+                                const std::string& act, long rows, long waves,
+                                long nontemporal);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -174,6 +181,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("residual") = py::none(), py::arg("act") = "none",
         py::arg("rows") = 0, py::arg("waves") = 0,
+        py::arg("nontemporal") = -1);
+  m.def("decode_linear_fp8", &decode_linear_fp8,
+        "y = act((x Wq^T) * w_scale + bias) + residual for 1 <= M <= 16 bf16 "
+        "rows, K % 64 == 0: e4m3 codes streamed once and decoded in "
+        "registers, one fp32 scale per output row, epilogue fused "
+        "(rows/waves/nontemporal: tuning overrides, default automatic)",
+        py::arg("x"), py::arg("wq"), py::arg("w_scale"),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(),
+        py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
         py::arg("nontemporal") = -1);
   m.def("topp_select", &topp_select, "top-p nucleus cutoff + draw");
   m.def("sample_token", &sample_token,

@@ -30,7 +30,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from paddlefleetx_amd.models.gpt.model import GPTModel, StaticKVCache
+from paddlefleetx_amd.models.gpt.model import (DecodeWeightCodes, GPTModel,
+                                              StaticKVCache)
 from paddlefleetx_amd.models.gpt.processor import get_logits_processor
 from paddlefleetx_amd.ops import decode_linear, sample_token, topp_sampling
 from paddlefleetx_amd.parallel.env import get_hcg
@@ -134,6 +135,46 @@ class GPTForGeneration(nn.Module):
                            "model-parallel size 1: staying on the existing "
                            "path")
             self.fused_decode_linear = False
+        # storage of the weights a fused decode step streams: "bf16" (the
+        # parameters) or "fp8" (e4m3 codes + one fp32 scale per output row,
+        # quantised once, kept NEXT TO the bf16 parameters)
+        self.decode_weight_dtype = str(cfg.get("decode_weight_dtype")
+                                       or "bf16")
+        if self.decode_weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(
+                "Generation.decode_weight_dtype must be 'bf16' or 'fp8', got "
+                f"{self.decode_weight_dtype!r}")
+        if self.decode_weight_dtype == "fp8" and \
+                not cfg.get("fused_decode_linear", False):
+            raise ValueError(
+                "Generation.decode_weight_dtype: fp8 needs "
+                "fused_decode_linear: true (only ops.decode_linear reads "
+                "fp8 weights)")
+        if self.decode_weight_dtype == "fp8" and not self.fused_decode_linear:
+            logger.warning("Generation.decode_weight_dtype: fp8 needs "
+                           "model-parallel size 1: staying on bf16 weights")
+            self.decode_weight_dtype = "bf16"
+        # a plain attribute, not a submodule: no state_dict entry, no cast
+        self._weight_codes = DecodeWeightCodes() \
+            if self.decode_weight_dtype == "fp8" else None
+
+    def _decode_weights(self):
+        """The weights a fused decode step streams: four linears per decoder
+        layer and the tied embedding."""
+        ws = []
+        for layer in self.gpt.layers:
+            if not hasattr(layer.ffn, "up_bias"):
+                continue  # an expert layer never takes the fused path
+            ws += [layer.attn.qkv.weight, layer.attn.out_proj.weight,
+                   layer.ffn.up.weight, layer.ffn.down.weight]
+        ws.append(self.gpt.embeddings.word_embeddings.weight)
+        return ws
+
+    def _refresh_weight_codes(self) -> None:
+        """Quantise what is new or was changed since the last call (a no-op
+        otherwise); outside any captured region."""
+        if self._weight_codes is not None:
+            self._weight_codes.refresh(self._decode_weights())
 
     # -- one forward --------------------------------------------------------
     def _logits(self, input_ids, position_ids, caches):
@@ -152,7 +193,8 @@ class GPTForGeneration(nn.Module):
                              dtype=attn.qkv.weight.dtype, device=device,
                              kv_dtype=self.kv_cache_dtype,
                              max_seq_len=max_seq_len,
-                             fused_decode_linear=self.fused_decode_linear)
+                             fused_decode_linear=self.fused_decode_linear,
+                             weight_codes=self._weight_codes)
 
     # -- fused sampling -----------------------------------------------------
     def _capacity(self, prompt_len: int) -> int:
@@ -183,8 +225,10 @@ class GPTForGeneration(nn.Module):
         hidden, _ = self.gpt(st["next_tokens"], pos, caches=cache,
                              use_cache=True)
         if self.fused_decode_linear:
-            logits = decode_linear(
-                hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight)
+            w, s = self.gpt.embeddings.word_embeddings.weight, None
+            if self._weight_codes is not None:
+                w, s = self._weight_codes.get(w)
+            logits = decode_linear(hidden[:, -1, :], w, weight_scale=s)
         else:
             logits = parallel_matmul(
                 hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight,
@@ -205,6 +249,7 @@ class GPTForGeneration(nn.Module):
         """Reset the state, prefill eagerly and sample the first token."""
         B, prompt_len = input_ids.shape
         n = prompt_len + self.max_length
+        self._refresh_weight_codes()
         cache = st["cache"]
         cache.lens.zero_()
         cache.max_len = 0
@@ -282,6 +327,7 @@ class GPTForGeneration(nn.Module):
         scalars, so they are part of the reuse key."""
         st = self._new_state(B, capacity, device, fixed=True)
         cache = st["cache"]
+        self._refresh_weight_codes()  # never inside the captured region
 
         def reset():
             cache.lens.zero_()

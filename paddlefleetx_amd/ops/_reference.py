@@ -218,6 +218,39 @@ def dequantize_kv_rows(codes: torch.Tensor, scale: torch.Tensor
     return codes.float() * scale.float()[..., None]
 
 
+def quantize_weight_rows(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-output-row fp8 quantisation of a linear's weight: w [N, K] ->
+    (codes [N, K] float8_e4m3fn, scale [N] fp32), the arithmetic of
+    quantize_kv_rows. One scale per row keeps the scale out of the k loop
+    (one multiply per output element) and an outlier row costs no other."""
+    assert w.dim() == 2, f"quantize_weight_rows: w must be [N, K], got {tuple(w.shape)}"
+    return quantize_kv_rows(w)
+
+
+def decode_linear_fp8(x: torch.Tensor, codes: torch.Tensor,
+                      w_scale: torch.Tensor,
+                      bias: Optional[torch.Tensor] = None,
+                      residual: Optional[torch.Tensor] = None,
+                      activation: Optional[str] = None) -> torch.Tensor:
+    """decode_linear over quantize_weight_rows codes, fp32 math:
+    y = act((x @ codes^T) * w_scale + bias) + residual, one cast to x.dtype.
+
+    x [..., K], codes [N, K] float8_e4m3fn, w_scale [N] fp32, bias [N],
+    residual [..., N]; activation None or "gelu". The scale multiplies the
+    finished sum, as in the kernel's epilogue.
+    """
+    assert activation in (None, "none", "gelu"), activation
+    yf = torch.matmul(x.float(), codes.float().t()) * w_scale.float()
+    if bias is not None:
+        yf = yf + bias.float()
+    if activation == "gelu":
+        yf = 0.5 * yf * (1.0 + torch.tanh(
+            0.7978845608028654 * (yf + 0.044715 * yf ** 3)))
+    if residual is not None:
+        yf = yf + residual.float()
+    return yf.to(x.dtype)
+
+
 def decode_attention_fp8(qkv: torch.Tensor, k_cache: torch.Tensor,
                          v_cache: torch.Tensor, k_scale: torch.Tensor,
                          v_scale: torch.Tensor, seq_lens: torch.Tensor,

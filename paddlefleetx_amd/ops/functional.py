@@ -229,28 +229,39 @@ def bias_gelu(x, bias=None):
 DECODE_LINEAR_MAX_M = 16
 
 
-def _decode_linear_fits(x2, weight, bias, residual) -> bool:
-    """The contract of the decode_linear kernel (csrc/decode_linear.hip);
-    straight-line, it runs on every call of the eager decode loop."""
+def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None) -> bool:
+    """The contract of the decode_linear kernels (csrc/decode_linear.hip;
+    csrc/decode_linear_fp8.hip when weight_scale is given: e4m3 weight, fp32
+    scale [N], K % 64 == 0 as a 16-byte load is 16 codes); straight-line, it
+    runs on every call of the eager decode loop."""
+    fp8 = weight_scale is not None
+    wdtype = torch.float8_e4m3fn if fp8 else torch.bfloat16
     if not (use_hip(x2) and x2.dtype == torch.bfloat16
-            and weight.dtype == torch.bfloat16 and weight.dim() == 2):
+            and weight.dtype == wdtype and weight.dim() == 2):
         return False
     M, K = x2.shape
     N = weight.shape[0]
-    if not (1 <= M <= DECODE_LINEAR_MAX_M and K >= 32 and K % 32 == 0
+    kstep = 64 if fp8 else 32
+    if not (1 <= M <= DECODE_LINEAR_MAX_M and K >= kstep and K % kstep == 0
             and N >= 8 and N % 8 == 0 and weight.shape[1] == K):
         return False
     grad = torch.is_grad_enabled()
-    for t in (x2, weight, bias, residual):
+    for t in (x2, bias, residual) + (() if fp8 else (weight,)):
         if t is not None and (
                 t.dtype != torch.bfloat16 or t.device != x2.device
                 or not t.is_contiguous() or (grad and t.requires_grad)):
             return False
+    if fp8 and not (
+            weight.device == x2.device and weight.is_contiguous()
+            and weight_scale.dtype == torch.float32
+            and weight_scale.device == x2.device
+            and weight_scale.shape == (N,) and weight_scale.is_contiguous()):
+        return False
     return x2.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
 
 
 def decode_linear(x, weight, bias=None, residual=None,
-                  activation: Optional[str] = None):
+                  activation: Optional[str] = None, weight_scale=None):
     """y = act(x @ weight^T + bias) + residual for the decode step
     (inference only; no autograd through the kernel).
 
@@ -264,6 +275,12 @@ def decode_linear(x, weight, bias=None, residual=None,
     through the epilogue and rounded to bf16 once. Every other case (CPU,
     fp32, M > 16, other K or N, strided operands, a tensor that requires
     grad with grad enabled) computes the same expression from library ops.
+
+    A float8_e4m3fn weight (ref.quantize_weight_rows codes) needs
+    weight_scale [N] fp32, one scale per output row, and gives
+    act((x @ codes^T) * weight_scale + bias) + residual: weight-only fp8,
+    bf16 activations. The fp8 kernel streams half the bytes and needs
+    K % 64 == 0; what does not fit it computes ref.decode_linear_fp8.
     """
     assert activation in (None, "none", "gelu"), \
         f"decode_linear: activation must be None or 'gelu', got {activation!r}"
@@ -272,6 +289,20 @@ def decode_linear(x, weight, bias=None, residual=None,
     N = weight.shape[0]
     x2 = x.reshape(-1, K)
     res2 = residual.reshape(-1, N) if residual is not None else None
+    if weight.dtype == torch.float8_e4m3fn:
+        if weight_scale is None:
+            raise ValueError(
+                "decode_linear: a float8_e4m3fn weight needs weight_scale")
+        if _decode_linear_fits(x2, weight, bias, res2, weight_scale):
+            y = hip_ext().decode_linear_fp8(x2, weight, weight_scale, bias,
+                                            res2, "gelu" if gelu else "none")
+            return y.view(*x.shape[:-1], N)
+        return ref.decode_linear_fp8(x, weight, weight_scale, bias, residual,
+                                     activation)
+    if weight_scale is not None:
+        raise ValueError(
+            "decode_linear: weight_scale goes with a float8_e4m3fn weight, "
+            f"got {weight.dtype}")
     if _decode_linear_fits(x2, weight, bias, res2):
         y = hip_ext().decode_linear(x2, weight, bias, res2,
                                     "gelu" if gelu else "none")

@@ -28,7 +28,8 @@ hip_sources = [
     os.path.join(CSRC, s)
     for s in ("bindings.cpp", "layernorm.hip", "elementwise.hip",
               "softmax.hip", "attention.hip", "decode_attention.hip",
-              "decode_attention_fp8.hip", "decode_linear.hip", "topp.hip",
+              "decode_attention_fp8.hip", "decode_linear.hip",
+              "decode_linear_fp8.hip", "topp.hip",
               "sample_token.hip", "moe.hip", "mfma_probe.hip")
 ]
 
