@@ -20,44 +20,15 @@
 // rounding to bf16) runs in the same launch. No counters, flags or atomics.
 //
 // Rows of W at index >= N, rows of x at index >= M and k-steps past a wave's
-// chunk are never loaded: the load sits behind a predicate (exec-masked,
-// as in decode_attention.hip), and nothing such a lane holds reaches a
-// stored element.
-#include "common.h"
-
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <cstdint>
-#include <string>
+// chunk are never loaded ("Masked lanes" in decode_linear_common.h, which
+// also holds the 16-byte load, the per-element epilogue and the binding's
+// checks, shared with decode_linear_fp8.hip).
+#include "decode_linear_common.h"
 
 namespace {
 
-constexpr int TILE = 16;     // MFMA rows (n) and columns (m)
 constexpr int KSTEP = 32;    // k per MFMA
 constexpr int U = 8;         // k-steps in flight: 16-byte loads per operand
-constexpr float GELU_K = 0.7978845608028654f;  // sqrt(2/pi)
-
-// the tanh-GELU of elementwise.hip (bias_gelu), same formula and exp unit
-DEV_INLINE float gelu_tanh(float x) {
-  const float t =
-      1.f - 2.f / (__expf(2.f * GELU_K * (x + 0.044715f * x * x * x)) + 1.f);
-  return 0.5f * x * (1.f + t);
-}
-
-template <bool NT>
-DEV_INLINE short8v load16(const short* p) {
-  if constexpr (NT)
-    return __builtin_nontemporal_load(reinterpret_cast<const short8v*>(p));
-  else
-    return *reinterpret_cast<const short8v*>(p);
-}
-
-DEV_INLINE mfma_bf16x8 as_frag(const short8v& v) {
-  union { short8v s; mfma_bf16x8 f; } u;
-  u.s = v;
-  return u.f;
-}
 
 // grid ceil(N / rows), NW*64 threads; rows = 16*TILES, or 8 with TILES = 1
 // (the upper half of the MFMA tile masked). The TILES tiles of a workgroup
@@ -72,6 +43,7 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_kernel(
     int M, int N, int K, int rows, int gelu) {
   __shared__ float s_part[NW][TILES * TILE * TILE];
 
+  // setup and reduction: same text in both kernels, see the header for why
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   // wave-uniform: keeps the chunk bounds and their branches scalar
@@ -101,10 +73,8 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_kernel(
   mfma_f32x4 acc[TILES];
 #pragma unroll
   for (int t = 0; t < TILES; ++t) acc[t] = mfma_f32x4{0.f, 0.f, 0.f, 0.f};
-  // Fragments of masked lanes are never loaded and need no zero: row n of C
-  // depends on row n of A alone and column m on column m of B alone, and
-  // the epilogue stores neither rows >= N nor columns >= M. They start as
-  // zero and keep whatever they held.
+  // Fragments of masked lanes are never loaded and need no zero ("Masked
+  // lanes" in decode_linear_common.h).
   const short8v zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   short8v a[TILES][U], b[U];
 #pragma unroll
@@ -124,13 +94,13 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_kernel(
         if (w_ok[t]) {
 #pragma unroll
           for (int u = 0; u < U; ++u)
-            a[t][u] = load16<NT>(wp[t] + off + u * KSTEP);
+            a[t][u] = load16<short8v, NT>(wp[t] + off + u * KSTEP);
         }
       }
       if (x_ok) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          b[u] = load16<false>(xp + off + u * KSTEP);
+          b[u] = load16<short8v, false>(xp + off + u * KSTEP);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -147,8 +117,9 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_kernel(
         if (u < nb) {
 #pragma unroll
           for (int t = 0; t < TILES; ++t)
-            if (w_ok[t]) a[t][u] = load16<NT>(wp[t] + off + u * KSTEP);
-          if (x_ok) b[u] = load16<false>(xp + off + u * KSTEP);
+            if (w_ok[t])
+              a[t][u] = load16<short8v, NT>(wp[t] + off + u * KSTEP);
+          if (x_ok) b[u] = load16<short8v, false>(xp + off + u * KSTEP);
         }
       }
 #pragma unroll
@@ -179,23 +150,13 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_kernel(
       float v = 0.f;
 #pragma unroll
       for (int i = 0; i < NW; ++i) v += s_part[i][e];
-      if (bias) v += bf_raw2f((unsigned short)bias[n]);
-      if (gelu) v = gelu_tanh(v);
-      const size_t o = (size_t)m * N + n;
-      if (res) v += bf_raw2f((unsigned short)res[o]);
-      y[o] = (short)f2bf_raw(v);
+      finish_element<false>(v, m, n, N, nullptr, bias, res, y, gelu);
     }
   }
 }
 
-struct Args {
-  const short *x, *w, *bias, *res;
-  short* y;
-  int M, N, K, rows, gelu;
-};
-
 template <int NW, int TILES, bool NT>
-void launch(const Args& a) {
+void launch(const Args<short>& a) {
   auto stream = at::hip::getCurrentHIPStream();
   const int grid = (a.N + a.rows - 1) / a.rows;
   hipLaunchKernelGGL((decode_linear_kernel<NW, TILES, NT>), dim3(grid),
@@ -204,7 +165,7 @@ void launch(const Args& a) {
 }
 
 template <int NW>
-void launch_tiles(const Args& a, bool nt) {
+void launch_tiles(const Args<short>& a, bool nt) {
   if (a.rows == 32) {
     if (nt) launch<NW, 2, true>(a);
     else launch<NW, 2, false>(a);
@@ -212,10 +173,6 @@ void launch_tiles(const Args& a, bool nt) {
     if (nt) launch<NW, 1, true>(a);
     else launch<NW, 1, false>(a);
   }
-}
-
-bool aligned16(const torch::Tensor& t) {
-  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
 }
 
 }  // namespace
@@ -227,63 +184,10 @@ torch::Tensor decode_linear(torch::Tensor x, torch::Tensor weight,
                             c10::optional<torch::Tensor> residual,
                             const std::string& act, long rows, long waves,
                             long nontemporal) {
-  TORCH_CHECK(x.defined() && weight.defined(),
-              "decode_linear: x and weight must be defined");
-  TORCH_CHECK(x.is_cuda() && weight.is_cuda(),
-              "decode_linear: x and weight must be GPU tensors");
-  TORCH_CHECK(weight.device() == x.device(),
-              "decode_linear: weight is on ", weight.device(), ", expected ",
-              x.device());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
-                  weight.scalar_type() == torch::kBFloat16,
-              "decode_linear: x and weight must be bfloat16, got ",
-              x.scalar_type(), " and ", weight.scalar_type());
-  TORCH_CHECK(x.dim() == 2 && weight.dim() == 2,
-              "decode_linear: x must be [M, K] and weight [N, K]");
-  TORCH_CHECK(x.is_contiguous(), "decode_linear: x must be contiguous");
-  TORCH_CHECK(weight.is_contiguous(),
-              "decode_linear: weight must be contiguous");
-  const long M = x.size(0), K = x.size(1), N = weight.size(0);
-  TORCH_CHECK(weight.size(1) == K, "decode_linear: weight must be [N, ", K,
-              "], got [", N, ", ", weight.size(1), "]");
-  TORCH_CHECK(M >= 1 && M <= TILE, "decode_linear: M must be in [1, 16], got ",
-              M);
-  TORCH_CHECK(K >= KSTEP && K % KSTEP == 0,
-              "decode_linear: K must be a positive multiple of 32, got ", K);
-  TORCH_CHECK(N >= 8 && N % 8 == 0,
-              "decode_linear: N must be a positive multiple of 8, got ", N);
-  TORCH_CHECK(N * K < (1L << 40) && N < (1L << 30) && K < (1L << 30),
-              "decode_linear: bad weight extent");
-  TORCH_CHECK(aligned16(x) && aligned16(weight),
-              "decode_linear: x and weight must be 16-byte aligned");
-  TORCH_CHECK(act == "none" || act == "gelu",
-              "decode_linear: act must be 'none' or 'gelu', got '", act, "'");
-  const short* bp = nullptr;
-  const short* rp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    const torch::Tensor& b = *bias;
-    TORCH_CHECK(b.scalar_type() == torch::kBFloat16 &&
-                    b.device() == x.device() && b.is_contiguous() &&
-                    b.dim() == 1 && b.size(0) == N,
-                "decode_linear: bias must be a contiguous bfloat16 [", N,
-                "] on ", x.device());
-    bp = (const short*)b.data_ptr();
-  }
-  if (residual.has_value() && residual->defined()) {
-    const torch::Tensor& rs = *residual;
-    TORCH_CHECK(rs.scalar_type() == torch::kBFloat16 &&
-                    rs.device() == x.device() && rs.is_contiguous() &&
-                    rs.dim() == 2 && rs.size(0) == M && rs.size(1) == N,
-                "decode_linear: residual must be a contiguous bfloat16 [", M,
-                ", ", N, "] on ", x.device());
-    rp = (const short*)rs.data_ptr();
-  }
-  TORCH_CHECK(rows == 0 || rows == 8 || rows == 16 || rows == 32,
-              "decode_linear: rows must be 0 (auto), 8, 16 or 32");
-  TORCH_CHECK(waves == 0 || waves == 4 || waves == 8,
-              "decode_linear: waves must be 0 (auto), 4 or 8");
-  TORCH_CHECK(nontemporal >= -1 && nontemporal <= 1,
-              "decode_linear: nontemporal must be -1 (auto), 0 or 1");
+  const Checked c = check_decode_linear(
+      "decode_linear", "weight", x, weight, torch::kBFloat16, KSTEP, bias,
+      residual, act, rows, {8, 16, 32}, waves, nontemporal);
+  const long M = c.M, N = c.N, K = c.K;
 
   // Measured choice (benchmarks/bench_decode_linear.py --sweep, KERNELS.md):
   // the most rows per workgroup that still give 3/4 of the CUs a workgroup,
@@ -304,9 +208,10 @@ torch::Tensor decode_linear(torch::Tensor x, torch::Tensor weight,
                                   : nontemporal != 0;
 
   auto y = torch::empty({M, N}, x.options());
-  const Args a{(const short*)x.data_ptr(), (const short*)weight.data_ptr(),
-               bp, rp, (short*)y.data_ptr(), (int)M, (int)N, (int)K,
-               (int)rows, act == "gelu"};
+  const Args<short> a{(const short*)x.data_ptr(),
+                      (const short*)weight.data_ptr(), nullptr, c.bias, c.res,
+                      (short*)y.data_ptr(), (int)M, (int)N, (int)K, (int)rows,
+                      act == "gelu"};
   if (waves == 4)
     launch_tiles<4>(a, nt);
   else

@@ -27,45 +27,16 @@
 // decoded matrix, and the one new rounding is the multiply by the scale.
 //
 // Rows of Wq and entries of w_scale at index >= N, rows of x at index >= M
-// and k-steps past a wave's chunk are never loaded: every such load sits
-// behind a predicate (exec-masked, valid base address), and nothing such a
-// lane holds reaches a stored element.
-#include "common.h"
-
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <cstdint>
-#include <string>
+// and k-steps past a wave's chunk are never loaded ("Masked lanes" in
+// decode_linear_common.h, which also holds the 16-byte load, the per-element
+// epilogue and the binding's checks, shared with decode_linear.hip).
+#include "decode_linear_common.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) int int4v;
 
-constexpr int TILE = 16;     // MFMA rows (n) and columns (m)
 constexpr int KSTEP = 64;    // k per 16-byte load of codes: two MFMAs
-constexpr float GELU_K = 0.7978845608028654f;  // sqrt(2/pi)
-
-// the tanh-GELU of elementwise.hip (bias_gelu) and decode_linear.hip
-DEV_INLINE float gelu_tanh(float x) {
-  const float t =
-      1.f - 2.f / (__expf(2.f * GELU_K * (x + 0.044715f * x * x * x)) + 1.f);
-  return 0.5f * x * (1.f + t);
-}
-
-template <bool NT>
-DEV_INLINE int4v load16(const void* p) {
-  if constexpr (NT)
-    return __builtin_nontemporal_load(reinterpret_cast<const int4v*>(p));
-  else
-    return *reinterpret_cast<const int4v*>(p);
-}
-
-DEV_INLINE mfma_bf16x8 as_frag(const int4v& v) {
-  union { int4v i; mfma_bf16x8 f; } u;
-  u.i = v;
-  return u.f;
-}
 
 // 8 e4m3 codes (two words) -> 8 bf16, exact: the high halves of the fp32 pair
 DEV_INLINE mfma_bf16x8 decode8(int w0, int w1) {
@@ -103,6 +74,7 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_fp8_kernel(
   constexpr int U = Flight<TILES>::U;
   __shared__ float s_part[NW][TILES * TILE * TILE];
 
+  // setup and reduction: same text in both kernels, see the header for why
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   // wave-uniform: keeps the chunk bounds and their branches scalar
@@ -132,10 +104,8 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_fp8_kernel(
   mfma_f32x4 acc[TILES];
 #pragma unroll
   for (int t = 0; t < TILES; ++t) acc[t] = mfma_f32x4{0.f, 0.f, 0.f, 0.f};
-  // Fragments of masked lanes are never loaded and need no zero: row n of C
-  // depends on row n of A alone and column m on column m of B alone, and
-  // the epilogue stores neither rows >= N nor columns >= M. They start as
-  // zero and keep whatever they held.
+  // Fragments of masked lanes are never loaded and need no zero ("Masked
+  // lanes" in decode_linear_common.h).
   const int4v zero4 = {0, 0, 0, 0};
   int4v a[TILES][U], b[U][2];
 #pragma unroll
@@ -162,15 +132,16 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_fp8_kernel(
         if (w_ok[t]) {
 #pragma unroll
           for (int u = 0; u < U; ++u)
-            if (u < nb) a[t][u] = load16<NT>(wp[t] + off + u * KSTEP);
+            if (u < nb)
+              a[t][u] = load16<int4v, NT>(wp[t] + off + u * KSTEP);
         }
       }
       if (x_ok) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           if (u < nb) {
-            b[u][0] = load16<false>(xp + off + u * KSTEP);
-            b[u][1] = load16<false>(xp + off + u * KSTEP + 8);
+            b[u][0] = load16<int4v, false>(xp + off + u * KSTEP);
+            b[u][1] = load16<int4v, false>(xp + off + u * KSTEP + 8);
           }
         }
       }
@@ -178,10 +149,11 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_fp8_kernel(
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (u < nb) {
-          if (w_ok[0]) a[0][u] = load16<NT>(wp[0] + off + u * KSTEP);
+          if (w_ok[0])
+            a[0][u] = load16<int4v, NT>(wp[0] + off + u * KSTEP);
           if (x_ok) {
-            b[u][0] = load16<false>(xp + off + u * KSTEP);
-            b[u][1] = load16<false>(xp + off + u * KSTEP + 8);
+            b[u][0] = load16<int4v, false>(xp + off + u * KSTEP);
+            b[u][1] = load16<int4v, false>(xp + off + u * KSTEP + 8);
           }
         }
       }
@@ -218,27 +190,13 @@ __global__ __launch_bounds__(NW * WAVE) void decode_linear_fp8_kernel(
       float v = 0.f;
 #pragma unroll
       for (int i = 0; i < NW; ++i) v += s_part[i][e];
-      v *= w_scale[n];
-      if (bias) v += bf_raw2f((unsigned short)bias[n]);
-      if (gelu) v = gelu_tanh(v);
-      const size_t o = (size_t)m * N + n;
-      if (res) v += bf_raw2f((unsigned short)res[o]);
-      y[o] = (short)f2bf_raw(v);
+      finish_element<true>(v, m, n, N, w_scale, bias, res, y, gelu);
     }
   }
 }
 
-struct Args {
-  const short* x;
-  const unsigned char* w;
-  const float* w_scale;
-  const short *bias, *res;
-  short* y;
-  int M, N, K, rows, gelu;
-};
-
 template <int NW, int TILES, bool NT>
-void launch(const Args& a) {
+void launch(const Args<unsigned char>& a) {
   auto stream = at::hip::getCurrentHIPStream();
   const int grid = (a.N + a.rows - 1) / a.rows;
   hipLaunchKernelGGL((decode_linear_fp8_kernel<NW, TILES, NT>), dim3(grid),
@@ -247,14 +205,10 @@ void launch(const Args& a) {
 }
 
 template <int NW, bool NT>
-void launch_tiles(const Args& a) {
+void launch_tiles(const Args<unsigned char>& a) {
   if (a.rows == 64) launch<NW, 4, NT>(a);
   else if (a.rows == 32) launch<NW, 2, NT>(a);
   else launch<NW, 1, NT>(a);
-}
-
-bool aligned16(const torch::Tensor& t) {
-  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
 }
 
 }  // namespace
@@ -267,70 +221,16 @@ torch::Tensor decode_linear_fp8(torch::Tensor x, torch::Tensor wq,
                                 c10::optional<torch::Tensor> residual,
                                 const std::string& act, long rows, long waves,
                                 long nontemporal) {
-  TORCH_CHECK(x.defined() && wq.defined() && w_scale.defined(),
-              "decode_linear_fp8: x, wq and w_scale must be defined");
-  TORCH_CHECK(x.is_cuda() && wq.is_cuda() && w_scale.is_cuda(),
-              "decode_linear_fp8: x, wq and w_scale must be GPU tensors");
-  TORCH_CHECK(wq.device() == x.device() && w_scale.device() == x.device(),
-              "decode_linear_fp8: wq and w_scale must be on ", x.device());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16,
-              "decode_linear_fp8: x must be bfloat16, got ", x.scalar_type());
-  TORCH_CHECK(wq.scalar_type() == torch::kFloat8_e4m3fn,
-              "decode_linear_fp8: wq must be float8_e4m3fn, got ",
-              wq.scalar_type());
-  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2,
-              "decode_linear_fp8: x must be [M, K] and wq [N, K]");
-  TORCH_CHECK(x.is_contiguous(), "decode_linear_fp8: x must be contiguous");
-  TORCH_CHECK(wq.is_contiguous(), "decode_linear_fp8: wq must be contiguous");
-  const long M = x.size(0), K = x.size(1), N = wq.size(0);
-  TORCH_CHECK(wq.size(1) == K, "decode_linear_fp8: wq must be [N, ", K,
-              "], got [", N, ", ", wq.size(1), "]");
-  TORCH_CHECK(M >= 1 && M <= TILE,
-              "decode_linear_fp8: M must be in [1, 16], got ", M);
-  TORCH_CHECK(K >= KSTEP && K % KSTEP == 0,
-              "decode_linear_fp8: K must be a positive multiple of 64, got ",
-              K);
-  TORCH_CHECK(N >= 8 && N % 8 == 0,
-              "decode_linear_fp8: N must be a positive multiple of 8, got ",
-              N);
-  TORCH_CHECK(N * K < (1L << 40) && N < (1L << 30) && K < (1L << 30),
-              "decode_linear_fp8: bad weight extent");
-  TORCH_CHECK(aligned16(x) && aligned16(wq),
-              "decode_linear_fp8: x and wq must be 16-byte aligned");
-  TORCH_CHECK(w_scale.scalar_type() == torch::kFloat32 &&
+  const Checked c = check_decode_linear(
+      "decode_linear_fp8", "wq", x, wq, torch::kFloat8_e4m3fn, KSTEP, bias,
+      residual, act, rows, {8, 16, 32, 64}, waves, nontemporal);
+  const long M = c.M, N = c.N;
+  TORCH_CHECK(w_scale.defined() && w_scale.device() == x.device() &&
+                  w_scale.scalar_type() == torch::kFloat32 &&
                   w_scale.is_contiguous() && w_scale.dim() == 1 &&
                   w_scale.size(0) == N,
               "decode_linear_fp8: w_scale must be a contiguous float32 [", N,
-              "]");
-  TORCH_CHECK(act == "none" || act == "gelu",
-              "decode_linear_fp8: act must be 'none' or 'gelu', got '", act,
-              "'");
-  const short* bp = nullptr;
-  const short* rp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    const torch::Tensor& b = *bias;
-    TORCH_CHECK(b.scalar_type() == torch::kBFloat16 &&
-                    b.device() == x.device() && b.is_contiguous() &&
-                    b.dim() == 1 && b.size(0) == N,
-                "decode_linear_fp8: bias must be a contiguous bfloat16 [", N,
-                "] on ", x.device());
-    bp = (const short*)b.data_ptr();
-  }
-  if (residual.has_value() && residual->defined()) {
-    const torch::Tensor& rs = *residual;
-    TORCH_CHECK(rs.scalar_type() == torch::kBFloat16 &&
-                    rs.device() == x.device() && rs.is_contiguous() &&
-                    rs.dim() == 2 && rs.size(0) == M && rs.size(1) == N,
-                "decode_linear_fp8: residual must be a contiguous bfloat16 [",
-                M, ", ", N, "] on ", x.device());
-    rp = (const short*)rs.data_ptr();
-  }
-  TORCH_CHECK(rows == 0 || rows == 8 || rows == 16 || rows == 32 || rows == 64,
-              "decode_linear_fp8: rows must be 0 (auto), 8, 16, 32 or 64");
-  TORCH_CHECK(waves == 0 || waves == 4 || waves == 8,
-              "decode_linear_fp8: waves must be 0 (auto), 4 or 8");
-  TORCH_CHECK(nontemporal >= -1 && nontemporal <= 1,
-              "decode_linear_fp8: nontemporal must be -1 (auto), 0 or 1");
+              "] on ", x.device());
 
   // Measured choice (benchmarks/bench_decode_linear.py --weight-dtype fp8
   // --sweep at M = 1 and 16, GPT-1.3B and 6.7B shapes, KERNELS.md). Half
@@ -352,10 +252,10 @@ torch::Tensor decode_linear_fp8(torch::Tensor x, torch::Tensor wq,
   const bool nt = nontemporal < 0 ? small_grid : nontemporal != 0;
 
   auto y = torch::empty({M, N}, x.options());
-  const Args a{(const short*)x.data_ptr(),
-               (const unsigned char*)wq.data_ptr(),
-               (const float*)w_scale.data_ptr(), bp, rp, (short*)y.data_ptr(),
-               (int)M, (int)N, (int)K, (int)rows, act == "gelu"};
+  const Args<unsigned char> a{
+      (const short*)x.data_ptr(), (const unsigned char*)wq.data_ptr(),
+      (const float*)w_scale.data_ptr(), c.bias, c.res, (short*)y.data_ptr(),
+      (int)M, (int)N, (int)c.K, (int)rows, act == "gelu"};
   if (waves == 4) {
     if (nt) launch_tiles<4, true>(a);
     else launch_tiles<4, false>(a);
