@@ -26,6 +26,11 @@ e4m3 codes, one fp32 scale per output row) against the bf16 decode_linear on
 the same shapes, the two alternating in one process; its bytes are N*K + 4*N.
 With --sweep it sweeps the fp8 kernel's variants instead. --model 6.7B takes
 the GPT-6.7B shapes (hidden 4096).
+
+--ln times the LayerNorm-prologue launch (ops.decode_linear(..., ln=...)) on
+the linears that follow a LayerNorm (qkv, ffn_up, logits) against the pair it
+replaces, layernorm then decode_linear, alternating in the same way; with
+either --weight-dtype.
 """
 
 import argparse
@@ -110,6 +115,9 @@ def main():
                    help="time the kernel's (rows, waves, nt) variants")
     p.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
                    help="fp8: the fp8-weight kernel against the bf16 one")
+    p.add_argument("--ln", action="store_true",
+                   help="one LN + linear launch against layernorm, then "
+                        "decode_linear")
     p.add_argument("--model", choices=sorted(HIDDEN), default="1.3B")
     p.add_argument("--ms", type=int, nargs="+", default=list(MS))
     p.add_argument("--only", nargs="+", default=None,
@@ -131,6 +139,9 @@ def main():
     fp8 = args.weight_dtype == "fp8"
     shapes = [sh for sh in layer_shapes(HIDDEN[args.model])
               if args.only is None or sh[0] in args.only]
+    if args.ln:
+        bench_ln(decode_linear, shapes, dev, args)
+        return
     if fp8:
         from paddlefleetx_amd.ops import _reference as ref
         bench_fp8(ext, ref, decode_linear, shapes, dev, args)
@@ -277,6 +288,53 @@ def bench_fp8(ext, ref, decode_linear, shapes, dev, args):
                   f"{u16 / u8:5.2f}x  (fp8 min/max {min(t8):.2f}/"
                   f"{max(t8):.2f}, bf16 {min(t16):.2f}/{max(t16):.2f}; "
                   f"worst pairing {min(t16) / max(t8):.2f}x)", flush=True)
+        del sets
+
+
+def bench_ln(decode_linear, shapes, dev, args):
+    """LN folded into the linear against layernorm + decode_linear, same
+    weights (bf16, or fp8 codes and scales) for both."""
+    from paddlefleetx_amd.ops import _reference as ref
+    from paddlefleetx_amd.ops import layernorm
+    bf16, fp8 = torch.bfloat16, args.weight_dtype == "fp8"
+    print(f"{'linear':>9} {'N':>6} {'K':>5} {'M':>3} | {'fused us':>9} | "
+          f"{'pair us':>9} | pair/fused")
+    for name, N, K, ep in shapes:
+        if name not in ("qkv", "ffn_up", "logits"):
+            continue
+        nsets = num_sets(N * K * (1 if fp8 else 2), args.max_sets)
+        sets = []
+        for _ in range(nsets):
+            w = (torch.randn(N, K, device=dev) * 0.02).to(bf16)
+            sets.append(ref.quantize_weight_rows(w) if fp8 else (w, None))
+        b = None if ep == "none" else torch.randn(N, device=dev).to(bf16)
+        act = "gelu" if ep == "bias_gelu" else None
+        g, beta = (torch.randn(K, device=dev).to(bf16) for _ in range(2))
+        for M in args.ms:
+            x = (torch.randn(M, K, device=dev) * 2 + 1).to(bf16)
+
+            def fused(s):
+                return decode_linear(x, s[0], b, None, act, weight_scale=s[1],
+                                     ln=(g, beta, 1e-5))
+
+            def pair(s):
+                return decode_linear(layernorm(x, g, beta, 1e-5), s[0], b,
+                                     None, act, weight_scale=s[1])
+
+            with torch.no_grad():
+                want = pair(sets[0]).float()
+                err = (fused(sets[0]).float() - want).abs().max().item()
+                # two bf16 ulps of the largest value
+                assert err <= 2.0 ** -6 * want.abs().max().item(), \
+                    f"fused and pair disagree: {err}"
+                (uf, up), (t_f, t_p) = alternate(
+                    (fused, pair), sets, args.iters, args.reps,
+                    not args.eager_launch)
+            print(f"{name:>9} {N:6d} {K:5d} {M:3d} | {uf:9.2f} | {up:9.2f} | "
+                  f"{up / uf:5.2f}x  (fused min/max {min(t_f):.2f}/"
+                  f"{max(t_f):.2f}, pair {min(t_p):.2f}/{max(t_p):.2f}; worst "
+                  f"pairing {min(t_p) / max(t_f):.2f}x; max|diff| {err:.4f})",
+                  flush=True)
         del sets
 
 

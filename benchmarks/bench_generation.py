@@ -7,7 +7,7 @@ Counterpart of the reference's inference latency harness
     python benchmarks/bench_generation.py [--model GPT-1.3B] \
         [--prompt-len 128] [--gen-len 64] \
         [--static-cache [--kv-dtype fp8] [--fused-sampling [--capture]] \
-         [--fused-linear [--weight-dtype fp8]]]
+         [--fused-linear [--weight-dtype fp8] [--fused-ln]]]
 """
 
 import argparse
@@ -55,6 +55,10 @@ def main():
                    help="storage of the weights the fused decode linears "
                         "stream (Generation.decode_weight_dtype); fp8 needs "
                         "--fused-linear")
+    p.add_argument("--fused-ln", action="store_true",
+                   help="ln1 / ln2 / final_ln of the decode step inside the "
+                        "qkv / ffn_up / logits launches "
+                        "(Generation.fused_decode_ln); needs --fused-linear")
     p.add_argument("--finish-check-interval", type=int, default=None,
                    help="Generation.finish_check_interval (fused sampling)")
     p.add_argument("--fixed-capacity", action="store_true",
@@ -68,6 +72,8 @@ def main():
         p.error("--fused-sampling needs --static-cache")
     if args.fused_linear and not args.static_cache:
         p.error("--fused-linear needs --static-cache")
+    if args.fused_ln and not args.fused_linear:
+        p.error("--fused-ln needs --fused-linear")
     if args.weight_dtype == "fp8" and not args.fused_linear:
         p.error("--weight-dtype fp8 needs --fused-linear")
 
@@ -100,6 +106,7 @@ def main():
             "capture_decode": args.capture,
             "fused_decode_linear": args.fused_linear,
             "decode_weight_dtype": args.weight_dtype,
+            "fused_decode_ln": args.fused_ln,
             **({"finish_check_interval": args.finish_check_interval}
                if args.finish_check_interval else {}),
             **({"kv_cache_capacity": args.prompt_len + args.gen_len}
@@ -112,7 +119,7 @@ def main():
           f"static_cache={args.static_cache} kv_dtype={args.kv_dtype} "
           f"fused_sampling={args.fused_sampling} capture={args.capture} "
           f"fused_linear={args.fused_linear} "
-          f"weight_dtype={args.weight_dtype} "
+          f"weight_dtype={args.weight_dtype} fused_ln={args.fused_ln} "
           f"({dev})")
     for bs in [int(b) for b in args.batches.split(",")]:
         ids = torch.randint(0, vocab - 2, (bs, args.prompt_len), device=dev)

@@ -87,14 +87,20 @@ torch::Tensor decode_linear(torch::Tensor x, torch::Tensor weight,
                             c10::optional<torch::Tensor> bias,
                             c10::optional<torch::Tensor> residual,
                             const std::string& act, long rows, long waves,
-                            long nontemporal);
+                            long nontemporal,
+                            c10::optional<torch::Tensor> ln_weight,
+                            c10::optional<torch::Tensor> ln_bias,
+                            double ln_eps);
 // decode_linear_fp8.hip
 torch::Tensor decode_linear_fp8(torch::Tensor x, torch::Tensor wq,
                                 torch::Tensor w_scale,
                                 c10::optional<torch::Tensor> bias,
                                 c10::optional<torch::Tensor> residual,
                                 const std::string& act, long rows, long waves,
-                                long nontemporal);
+                                long nontemporal,
+                                c10::optional<torch::Tensor> ln_weight,
+                                c10::optional<torch::Tensor> ln_bias,
+                                double ln_eps);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -177,20 +183,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_linear", &decode_linear,
         "y = act(x W^T + bias) + residual for 1 <= M <= 16 bf16 rows: W "
         "streamed once, epilogue fused (rows/waves/nontemporal: tuning "
-        "overrides, default automatic)",
+        "overrides, default automatic); ln_weight + ln_bias: x is "
+        "LayerNorm'ed in the same launch",
         py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("residual") = py::none(), py::arg("act") = "none",
         py::arg("rows") = 0, py::arg("waves") = 0,
-        py::arg("nontemporal") = -1);
+        py::arg("nontemporal") = -1, py::arg("ln_weight") = py::none(),
+        py::arg("ln_bias") = py::none(), py::arg("ln_eps") = 1e-5);
   m.def("decode_linear_fp8", &decode_linear_fp8,
         "y = act((x Wq^T) * w_scale + bias) + residual for 1 <= M <= 16 bf16 "
         "rows, K % 64 == 0: e4m3 codes streamed once and decoded in "
         "registers, one fp32 scale per output row, epilogue fused "
-        "(rows/waves/nontemporal: tuning overrides, default automatic)",
+        "(rows/waves/nontemporal: tuning overrides, default automatic); "
+        "ln_weight + ln_bias: x is LayerNorm'ed in the same launch",
         py::arg("x"), py::arg("wq"), py::arg("w_scale"),
         py::arg("bias") = py::none(), py::arg("residual") = py::none(),
         py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
-        py::arg("nontemporal") = -1);
+        py::arg("nontemporal") = -1, py::arg("ln_weight") = py::none(),
+        py::arg("ln_bias") = py::none(), py::arg("ln_eps") = 1e-5);
   m.def("topp_select", &topp_select, "top-p nucleus cutoff + draw");
   m.def("sample_token", &sample_token,
         "logits row -> next token in one launch (min length, repetition "

@@ -3,7 +3,9 @@
 // 16-byte load and the fragment cast, the tanh-GELU, the per-element
 // epilogue, the launch arguments and every host-side check the two bindings
 // have in common. A fix applied to one copy of these alone would give wrong
-// numbers and no crash.
+// numbers and no crash. It also holds the LayerNorm prologue of the two
+// *_ln_kernel (statistics, variance rule, fragment normalisation), which is
+// not tied to the weight type; see "LayerNorm prologue" below.
 //
 // The main loops are NOT here. They are the measured part and they differ on
 // purpose: the bf16 kernel has a specialised path for full batches of
@@ -19,7 +21,8 @@
 // address arithmetic), which changed the schedule and register allocation
 // of every instance. The condition for this header is gfx950 ISA identical
 // to the unshared kernels (profiles/decode_linear_shared_header.txt); what
-// is here meets it.
+// is here meets it, and the kernels without LN are still ISA identical
+// with the LN prologue next to them (profiles/decode_linear_ln.txt).
 //
 // Masked lanes. Rows of W at index >= N, rows of x at index >= M and k-steps
 // past a wave's chunk are never loaded: every such load sits behind a
@@ -38,6 +41,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <cmath>
 #include <cstdint>
 #include <initializer_list>
 #include <string>
@@ -86,9 +90,172 @@ DEV_INLINE void finish_element(float v, int m, int n, int N,
   y[o] = (short)f2bf_raw(v);
 }
 
+// ---- LayerNorm prologue (the *_ln_kernel of both files) ----
+//
+// y = act(LN(x) . W^T ...) with LN(x) = bf16((x - mu) * rstd * g + b): the
+// statistics of the <= 16 rows are computed by every workgroup (x is in L2,
+// and there is no way to hand them over without a flag or a second launch),
+// then every x fragment is normalised in registers on its way into the MFMA.
+// Same roundings as layernorm + decode_linear: h to bf16 once, y once.
+//
+// Not tied to the weight type: a k-step is XL 16-byte loads of x per lane
+// (1 with bf16 weights, 2 with fp8 codes), the l-th at xp + step*KSTEP + 8*l.
+
+// largest K of the LN kernels: g and b sit in LDS (4*K bytes) next to the
+// partial tiles, at most 32 KiB + 1.5 KiB of statistics; 64 KiB in all
+constexpr int LN_MAX_K = 7168;
+// 16-byte loads in flight per lane in the statistics passes (LN_LOADS / XL
+// k-steps): a wave's whole chunk at K = 2048, so a pass is one trip to L2
+constexpr int LN_LOADS = 16;
+
+// On the LN kernels: their fp32 arithmetic on pairs of bf16 (statistics,
+// normalisation) is compiled to scalar-per-lane VALU ops, never to the
+// packed v_pk_*_f32 forms. The kernels without LN hold no such arithmetic.
+#define NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+DEV_INLINE float bf_lo(unsigned int w) { return __uint_as_float(w << 16); }
+DEV_INLINE float bf_hi(unsigned int w) {
+  return __uint_as_float(w & 0xffff0000u);
+}
+
+// sum over the wave's four lane groups: lanes r, r+16, r+32, r+48 hold the
+// k slices of one row. Every one of them ends with the same bits.
+DEV_INLINE float ln_group_sum(float v) {
+  v += __shfl_xor(v, 16, WAVE);
+  v += __shfl_xor(v, 32, WAVE);
+  return v;
+}
+
+// One pass over the wave's k-steps [s_beg, s_end) with the addressing and
+// the predicate of its B fragments. DEV false: s += x, q += x*x; DEV true:
+// q += (x - mu)^2. Masked lanes load nothing and keep zeros. between() runs
+// once, in every lane, after the first batch of loads is issued and before
+// it is waited for.
+template <typename V, int KSTEP, int XL, bool DEV, typename F>
+DEV_INLINE void ln_pass(const short* xp, bool x_ok, int s_beg, int s_end,
+                        float mu, float& s, float& q, F between) {
+  constexpr int LN_SU = LN_LOADS / XL;
+  for (int st = s_beg; st < s_end; st += LN_SU) {
+    const int nb = s_end - st;  // wave-uniform
+    union { V v; unsigned int w[4]; } f[LN_SU][XL];
+    if (x_ok) {
+#pragma unroll
+      for (int u = 0; u < LN_SU; ++u) {
+        if (u < nb) {
+#pragma unroll
+          for (int l = 0; l < XL; ++l)
+            f[u][l].v =
+                load16<V, false>(xp + (size_t)(st + u) * KSTEP + 8 * l);
+        }
+      }
+    }
+    if (st == s_beg) between();
+    if (x_ok) {
+#pragma unroll
+      for (int u = 0; u < LN_SU; ++u) {
+        if (u < nb) {
+#pragma unroll
+          for (int l = 0; l < XL; ++l) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const float lo = bf_lo(f[u][l].w[i]), hi = bf_hi(f[u][l].w[i]);
+              if constexpr (DEV) {
+                q += (lo - mu) * (lo - mu);
+                q += (hi - mu) * (hi - mu);
+              } else {
+                s += lo;
+                q += lo * lo;
+                s += hi;
+                q += hi * hi;
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+// mu and rstd of the lane's row (lane & 15) from the whole workgroup, and g
+// and b staged into s_gb ([0, K): g, [K, 2K): b) under the same barrier.
+// Each wave sums the chunk it is about to stream, writes one (sum, sumsq)
+// per row, and after the barrier every lane adds the NW partials of its row
+// in wave order; a wave with an empty chunk contributes zeros. The variance
+// rule is layernorm.hip's: E[x^2] - mu^2 where that is >= E[x^2] / 4, else
+// a second pass over (x - mu)^2. All waves read the same partials, so the
+// ballot is the same in every wave and the second barrier is reached by all
+// or none; a row that passes the test keeps its one-pass variance whatever
+// the other rows do.
+// first_w() issues the wave's first batch of weight loads. It runs behind
+// the x loads of the statistics pass and ahead of their wait: loads return
+// in issue order, so the statistics are computed, exchanged and turned into
+// mu and rstd while the weights are on their way from HBM.
+template <typename V, int NW, int KSTEP, int XL, typename F>
+DEV_INLINE void ln_prologue(const short* xp, bool x_ok, int s_beg, int s_end,
+                            int K, const short* ln_w, const short* ln_b,
+                            float eps, short* s_gb, float (*s_stat)[2 * TILE],
+                            float (*s_dev)[TILE], int tid, int wid, int r,
+                            float& mu, float& rstd, F first_w) {
+  float s = 0.f, q = 0.f;
+  ln_pass<V, KSTEP, XL, false>(xp, x_ok, s_beg, s_end, 0.f, s, q, first_w);
+  s = ln_group_sum(s);
+  q = ln_group_sum(q);
+  if ((tid & (WAVE - 1)) < TILE) {
+    s_stat[wid][2 * r] = s;
+    s_stat[wid][2 * r + 1] = q;
+  }
+  for (int i = tid * 8; i < K; i += NW * WAVE * 8) {  // K % 8 == 0
+    *reinterpret_cast<V*>(s_gb + i) = load16<V, false>(ln_w + i);
+    *reinterpret_cast<V*>(s_gb + K + i) = load16<V, false>(ln_b + i);
+  }
+  __syncthreads();
+  s = 0.f;
+  q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    s += s_stat[i][2 * r];
+    q += s_stat[i][2 * r + 1];
+  }
+  mu = s / K;
+  const float ex2 = q / K;
+  float var = ex2 - mu * mu;
+  const bool redo = x_ok && !(var >= 0.25f * ex2);
+  if (__builtin_amdgcn_ballot_w64(redo) != 0) {  // workgroup-uniform
+    float d = 0.f, unused = 0.f;
+    ln_pass<V, KSTEP, XL, true>(xp, x_ok, s_beg, s_end, mu, unused, d,
+                                [] {});
+    d = ln_group_sum(d);
+    if ((tid & (WAVE - 1)) < TILE) s_dev[wid][r] = d;
+    __syncthreads();
+    d = 0.f;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) d += s_dev[i][r];
+    if (redo) var = d / K;
+  }
+  rstd = rsqrtf(var + eps);
+}
+
+// The B fragment of one 16-byte load of x at k: 8 values normalised in fp32
+// in layernorm.hip's expression order and rounded to bf16 (RNE).
+template <typename V>
+DEV_INLINE mfma_bf16x8 ln_frag(const V& xv, const short* s_gb, int K,
+                               size_t k, float mu, float rstd) {
+  union { V v; unsigned int w[4]; } x, g, b, o;
+  x.v = xv;
+  g.v = *reinterpret_cast<const V*>(s_gb + k);
+  b.v = *reinterpret_cast<const V*>(s_gb + K + k);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    o.w[i] = cvt_pk_bf16(
+        (bf_lo(x.w[i]) - mu) * rstd * bf_lo(g.w[i]) + bf_lo(b.w[i]),
+        (bf_hi(x.w[i]) - mu) * rstd * bf_hi(g.w[i]) + bf_hi(b.w[i]));
+  return as_frag(o.v);
+}
+
 // ---- host side ----
 
-// What a launch takes; w_scale stays null for bf16 weights.
+// What a launch takes; w_scale stays null for bf16 weights, ln_w and ln_b
+// without a LayerNorm prologue.
 template <typename WT>
 struct Args {
   const short* x;
@@ -97,6 +264,8 @@ struct Args {
   const short *bias, *res;
   short* y;
   int M, N, K, rows, gelu;
+  const short *ln_w, *ln_b;
+  float ln_eps;
 };
 
 bool aligned16(const torch::Tensor& t) {
@@ -105,7 +274,8 @@ bool aligned16(const torch::Tensor& t) {
 
 struct Checked {
   long M, N, K;
-  const short *bias, *res;  // null when absent
+  const short *bias, *res;    // null when absent
+  const short *ln_w, *ln_b;   // both null, or the LayerNorm prologue's
 };
 
 // Everything that stands between raw pointers and a launch and is the same
@@ -118,7 +288,10 @@ Checked check_decode_linear(const char* op, const char* wname,
                             const c10::optional<torch::Tensor>& residual,
                             const std::string& act, long rows,
                             std::initializer_list<long> rows_ok, long waves,
-                            long nontemporal) {
+                            long nontemporal,
+                            const c10::optional<torch::Tensor>& ln_weight,
+                            const c10::optional<torch::Tensor>& ln_bias,
+                            double ln_eps) {
   TORCH_CHECK(x.defined() && w.defined(), op, ": x and ", wname,
               " must be defined");
   TORCH_CHECK(x.is_cuda() && w.is_cuda(), op, ": x and ", wname,
@@ -147,7 +320,29 @@ Checked check_decode_linear(const char* op, const char* wname,
               " must be 16-byte aligned");
   TORCH_CHECK(act == "none" || act == "gelu", op,
               ": act must be 'none' or 'gelu', got '", act, "'");
-  Checked c{M, N, K, nullptr, nullptr};
+  Checked c{M, N, K, nullptr, nullptr, nullptr, nullptr};
+  const bool has_g = ln_weight.has_value() && ln_weight->defined();
+  const bool has_b = ln_bias.has_value() && ln_bias->defined();
+  TORCH_CHECK(has_g == has_b, op,
+              ": ln_weight and ln_bias go together (LayerNorm without a bias "
+              "is not built)");
+  if (has_g) {
+    for (const torch::Tensor* t : {&*ln_weight, &*ln_bias}) {
+      TORCH_CHECK(t->scalar_type() == torch::kBFloat16 &&
+                      t->device() == x.device() && t->is_contiguous() &&
+                      t->dim() == 1 && t->size(0) == K,
+                  op, ": ln_weight and ln_bias must be contiguous bfloat16 [",
+                  K, "] on ", x.device());
+      TORCH_CHECK(aligned16(*t), op,
+                  ": ln_weight and ln_bias must be 16-byte aligned");
+    }
+    TORCH_CHECK(std::isfinite(ln_eps) && ln_eps > 0, op,
+                ": ln_eps must be finite and positive, got ", ln_eps);
+    TORCH_CHECK(K <= LN_MAX_K, op, ": K must be <= ", LN_MAX_K,
+                " with a LayerNorm prologue, got ", K);
+    c.ln_w = (const short*)ln_weight->data_ptr();
+    c.ln_b = (const short*)ln_bias->data_ptr();
+  }
   if (bias.has_value() && bias->defined()) {
     const torch::Tensor& b = *bias;
     TORCH_CHECK(b.scalar_type() == torch::kBFloat16 &&

@@ -154,6 +154,18 @@ class GPTForGeneration(nn.Module):
             logger.warning("Generation.decode_weight_dtype: fp8 needs "
                            "model-parallel size 1: staying on bf16 weights")
             self.decode_weight_dtype = "bf16"
+        # ln1 / ln2 / final_ln of a fused decode step inside the qkv / ffn_up
+        # / logits launches (ops.decode_linear(..., ln=...))
+        self.fused_decode_ln = bool(cfg.get("fused_decode_ln", False))
+        if self.fused_decode_ln and \
+                not cfg.get("fused_decode_linear", False):
+            raise ValueError(
+                "Generation.fused_decode_ln: true needs fused_decode_linear: "
+                "true (the LayerNorm rides in ops.decode_linear)")
+        if self.fused_decode_ln and not self.fused_decode_linear:
+            logger.warning("Generation.fused_decode_ln needs model-parallel "
+                           "size 1: staying on separate LayerNorms")
+            self.fused_decode_ln = False
         # a plain attribute, not a submodule: no state_dict entry, no cast
         self._weight_codes = DecodeWeightCodes() \
             if self.decode_weight_dtype == "fp8" else None
@@ -194,7 +206,8 @@ class GPTForGeneration(nn.Module):
                              kv_dtype=self.kv_cache_dtype,
                              max_seq_len=max_seq_len,
                              fused_decode_linear=self.fused_decode_linear,
-                             weight_codes=self._weight_codes)
+                             weight_codes=self._weight_codes,
+                             fused_decode_ln=self.fused_decode_ln)
 
     # -- fused sampling -----------------------------------------------------
     def _capacity(self, prompt_len: int) -> int:
@@ -223,12 +236,17 @@ class GPTForGeneration(nn.Module):
         cache = st["cache"]
         pos = cache.lens.long().unsqueeze(1)
         hidden, _ = self.gpt(st["next_tokens"], pos, caches=cache,
-                             use_cache=True)
+                             use_cache=True,
+                             apply_final_ln=not self.fused_decode_ln)
         if self.fused_decode_linear:
             w, s = self.gpt.embeddings.word_embeddings.weight, None
             if self._weight_codes is not None:
                 w, s = self._weight_codes.get(w)
-            logits = decode_linear(hidden[:, -1, :], w, weight_scale=s)
+            ln = self.gpt.final_ln
+            logits = decode_linear(
+                hidden[:, -1, :], w, weight_scale=s,
+                ln=(ln.weight, ln.bias, ln.eps)
+                if self.fused_decode_ln else None)
         else:
             logits = parallel_matmul(
                 hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight,

@@ -149,6 +149,10 @@ class StaticKVCache:
     that decode one token against this cache run their linears through
     ops.decode_linear (TransformerDecoderLayer._forward_decode_fused).
 
+    fused_decode_ln (Generation.fused_decode_ln, needs fused_decode_linear):
+    those layers hand ln1 and ln2 to the qkv and ffn_up launches
+    (ops.decode_linear(..., ln=...)) instead of running them on their own.
+
     weight_codes (Generation.decode_weight_dtype: fp8): a DecodeWeightCodes
     those layers take fp8 codes and scales from instead of the bf16
     weights; None (the default) streams the parameters themselves.
@@ -160,7 +164,8 @@ class StaticKVCache:
                  kv_dtype: Optional[str] = None,
                  max_seq_len: Optional[int] = None,
                  fused_decode_linear: bool = False,
-                 weight_codes: Optional[DecodeWeightCodes] = None):
+                 weight_codes: Optional[DecodeWeightCodes] = None,
+                 fused_decode_ln: bool = False):
         assert kv_dtype in (None, "bf16", "fp8"), \
             f"StaticKVCache: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}"
         self.kv_dtype = "fp8" if kv_dtype == "fp8" else "bf16"
@@ -172,6 +177,9 @@ class StaticKVCache:
         assert weight_codes is None or self.fused_decode_linear, \
             "StaticKVCache: weight_codes needs fused_decode_linear"
         self.weight_codes = weight_codes
+        self.fused_decode_ln = bool(fused_decode_ln)
+        assert not self.fused_decode_ln or self.fused_decode_linear, \
+            "StaticKVCache: fused_decode_ln needs fused_decode_linear"
         shape = (batch_size, num_heads, self.capacity, head_dim)
         if self.kv_dtype == "fp8":
             dtype = torch.float8_e4m3fn
@@ -507,25 +515,31 @@ class TransformerDecoderLayer(nn.Module):
     def _forward_decode_fused(self, x, slot: StaticKVSlot):
         """One decode token with every linear as a decode_linear launch
         (bias, GELU and the residual adds ride in the epilogues): 7
-        launches plus the attention merge."""
+        launches plus the attention merge; 5 with the cache's
+        fused_decode_ln, where ln1 and ln2 ride in the qkv and ffn_up
+        launches (the residuals stay the un-normalised x and y)."""
         attn, ffn = self.attn, self.ffn
         codes = slot.owner.weight_codes
+        ln1 = ln2 = None
+        if slot.owner.fused_decode_ln:
+            ln1 = (self.ln1.weight, self.ln1.bias, self.ln1.eps)
+            ln2 = (self.ln2.weight, self.ln2.bias, self.ln2.eps)
 
         def wq(weight):
             # (weight, weight_scale): fp8 codes when the cache carries them
             return codes.get(weight) if codes is not None else (weight, None)
 
-        h = self.ln1(x)
+        h = x if ln1 else self.ln1(x)
         w, s = wq(attn.qkv.weight)
-        qkv = decode_linear(h, w, attn.qkv.bias, weight_scale=s)
+        qkv = decode_linear(h, w, attn.qkv.bias, weight_scale=s, ln=ln1)
         o = attn._decode_core(qkv, slot)
         w, s = wq(attn.out_proj.weight)
         y = decode_linear(o, w, attn.out_proj.bias, residual=x,
                           weight_scale=s)
-        h2 = self.ln2(y)
+        h2 = y if ln2 else self.ln2(y)
         w, s = wq(ffn.up.weight)
         u = decode_linear(h2, w, ffn.up_bias, activation="gelu",
-                          weight_scale=s)
+                          weight_scale=s, ln=ln2)
         w, s = wq(ffn.down.weight)
         return decode_linear(u, w, ffn.down.bias, residual=y, weight_scale=s)
 
@@ -647,7 +661,10 @@ class GPTModel(nn.Module):
             sp_ops.mark_as_sp_param(self.final_ln.bias)
 
     def forward(self, input_ids, position_ids=None,
-                caches: Optional[List[KVCache]] = None, use_cache: bool = False):
+                caches: Optional[List[KVCache]] = None, use_cache: bool = False,
+                apply_final_ln: bool = True):
+        """apply_final_ln=False returns the hidden state BEFORE final_ln
+        (the caller folds final_ln into what reads it)."""
         x = self.embeddings(input_ids, position_ids)
         new_caches: List[KVCache] = []
         for i, layer in enumerate(self.layers):
@@ -666,7 +683,8 @@ class GPTModel(nn.Module):
             # every layer appended at the same lens; move them once
             caches.advance(input_ids.shape[1])
             new_caches = caches
-        x = self.final_ln(x)
+        if apply_final_ln:
+            x = self.final_ln(x)
         if self.sequence_parallel:
             x = sp_ops.gather_from_sp_region(x)
         if use_cache:

@@ -102,16 +102,28 @@ def bias_gelu_bwd(dy: torch.Tensor, x: torch.Tensor, bias: Optional[torch.Tensor
     return dx.to(x.dtype), db
 
 
+def _ln_rows(x: torch.Tensor, ln: Optional[tuple]) -> torch.Tensor:
+    """x, or layernorm_fwd over its last dimension for ln = (w, b, eps)."""
+    if ln is None:
+        return x
+    w, b, eps = ln
+    y, _, _ = layernorm_fwd(x.reshape(-1, x.shape[-1]), w, b, eps)
+    return y.view(x.shape)
+
+
 def decode_linear(x: torch.Tensor, weight: torch.Tensor,
                   bias: Optional[torch.Tensor] = None,
                   residual: Optional[torch.Tensor] = None,
-                  activation: Optional[str] = None) -> torch.Tensor:
+                  activation: Optional[str] = None,
+                  ln: Optional[tuple] = None) -> torch.Tensor:
     """y = act(x @ weight^T + bias) + residual in fp32, one cast to x.dtype.
 
     x [..., K], weight [N, K], bias [N], residual [..., N]; activation None
-    or "gelu" (the tanh form of bias_gelu_fwd).
+    or "gelu" (the tanh form of bias_gelu_fwd). ln = (ln_weight, ln_bias,
+    eps): x is replaced by LayerNorm(x) rounded to x.dtype (layernorm_fwd).
     """
     assert activation in (None, "none", "gelu"), activation
+    x = _ln_rows(x, ln)
     yf = torch.matmul(x.float(), weight.float().t())
     if bias is not None:
         yf = yf + bias.float()
@@ -231,15 +243,17 @@ def decode_linear_fp8(x: torch.Tensor, codes: torch.Tensor,
                       w_scale: torch.Tensor,
                       bias: Optional[torch.Tensor] = None,
                       residual: Optional[torch.Tensor] = None,
-                      activation: Optional[str] = None) -> torch.Tensor:
+                      activation: Optional[str] = None,
+                      ln: Optional[tuple] = None) -> torch.Tensor:
     """decode_linear over quantize_weight_rows codes, fp32 math:
     y = act((x @ codes^T) * w_scale + bias) + residual, one cast to x.dtype.
 
     x [..., K], codes [N, K] float8_e4m3fn, w_scale [N] fp32, bias [N],
     residual [..., N]; activation None or "gelu". The scale multiplies the
-    finished sum, as in the kernel's epilogue.
+    finished sum, as in the kernel's epilogue. ln as in decode_linear.
     """
     assert activation in (None, "none", "gelu"), activation
+    x = _ln_rows(x, ln)
     yf = torch.matmul(x.float(), codes.float().t()) * w_scale.float()
     if bias is not None:
         yf = yf + bias.float()

@@ -227,9 +227,28 @@ def bias_gelu(x, bias=None):
 # ---------------------------------------------------------------------------
 
 DECODE_LINEAR_MAX_M = 16
+DECODE_LINEAR_LN_MAX_K = 7168  # LN_MAX_K of csrc/decode_linear_common.h
 
 
-def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None) -> bool:
+def _decode_linear_ln_fits(x2, ln) -> bool:
+    """The LayerNorm prologue's part of the contract: bf16 contiguous
+    16-byte aligned gamma and beta [K] on x's device, K <= 7168 (they are
+    staged in LDS), a finite positive eps."""
+    g, b, eps = ln
+    K = x2.shape[1]
+    if not (K <= DECODE_LINEAR_LN_MAX_K and math.isfinite(eps) and eps > 0):
+        return False
+    grad = torch.is_grad_enabled()
+    for t in (g, b):
+        if (t.dtype != torch.bfloat16 or t.device != x2.device
+                or t.shape != (K,) or not t.is_contiguous()
+                or t.data_ptr() % 16 != 0 or (grad and t.requires_grad)):
+            return False
+    return True
+
+
+def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None,
+                        ln=None) -> bool:
     """The contract of the decode_linear kernels (csrc/decode_linear.hip;
     csrc/decode_linear_fp8.hip when weight_scale is given: e4m3 weight, fp32
     scale [N], K % 64 == 0 as a 16-byte load is 16 codes); straight-line, it
@@ -257,11 +276,14 @@ def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None) -> bool:
             and weight_scale.device == x2.device
             and weight_scale.shape == (N,) and weight_scale.is_contiguous()):
         return False
+    if ln is not None and not _decode_linear_ln_fits(x2, ln):
+        return False
     return x2.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
 
 
 def decode_linear(x, weight, bias=None, residual=None,
-                  activation: Optional[str] = None, weight_scale=None):
+                  activation: Optional[str] = None, weight_scale=None,
+                  ln=None):
     """y = act(x @ weight^T + bias) + residual for the decode step
     (inference only; no autograd through the kernel).
 
@@ -281,6 +303,15 @@ def decode_linear(x, weight, bias=None, residual=None,
     act((x @ codes^T) * weight_scale + bias) + residual: weight-only fp8,
     bf16 activations. The fp8 kernel streams half the bytes and needs
     K % 64 == 0; what does not fit it computes ref.decode_linear_fp8.
+
+    ln = (ln_weight, ln_bias, eps) puts a LayerNorm in front:
+    decode_linear(layernorm(x, ln_weight, ln_bias, eps), ...) with the same
+    two roundings (LN(x) to bf16, y to bf16) in ONE launch: every workgroup
+    computes the statistics of the <= 16 rows and normalises its x
+    fragments in registers. Needs bf16 contiguous 16-byte aligned ln_weight
+    and ln_bias [K] and K <= 7168 on top of the contract above; every other
+    case (fp32 LN parameters included) runs layernorm, then this op
+    without ln.
     """
     assert activation in (None, "none", "gelu"), \
         f"decode_linear: activation must be None or 'gelu', got {activation!r}"
@@ -289,13 +320,27 @@ def decode_linear(x, weight, bias=None, residual=None,
     N = weight.shape[0]
     x2 = x.reshape(-1, K)
     res2 = residual.reshape(-1, N) if residual is not None else None
+    lnk = {}
+    if ln is not None:
+        g, b, eps = ln
+        if g is None or b is None:
+            raise ValueError("decode_linear: ln needs both ln_weight and "
+                             "ln_bias (LayerNorm without a bias is not built)")
+        if not _decode_linear_fits(x2, weight, bias, res2, weight_scale, ln):
+            # layernorm reads its parameters in 16-byte vectors
+            g, b = (t if t.data_ptr() % 16 == 0 else t.clone()
+                    for t in (g, b))
+            return decode_linear(layernorm(x, g, b, eps), weight, bias,
+                                 residual, activation, weight_scale)
+        lnk = dict(ln_weight=g, ln_bias=b, ln_eps=float(eps))
     if weight.dtype == torch.float8_e4m3fn:
         if weight_scale is None:
             raise ValueError(
                 "decode_linear: a float8_e4m3fn weight needs weight_scale")
         if _decode_linear_fits(x2, weight, bias, res2, weight_scale):
             y = hip_ext().decode_linear_fp8(x2, weight, weight_scale, bias,
-                                            res2, "gelu" if gelu else "none")
+                                            res2, "gelu" if gelu else "none",
+                                            **lnk)
             return y.view(*x.shape[:-1], N)
         return ref.decode_linear_fp8(x, weight, weight_scale, bias, residual,
                                      activation)
@@ -305,7 +350,7 @@ def decode_linear(x, weight, bias=None, residual=None,
             f"got {weight.dtype}")
     if _decode_linear_fits(x2, weight, bias, res2):
         y = hip_ext().decode_linear(x2, weight, bias, res2,
-                                    "gelu" if gelu else "none")
+                                    "gelu" if gelu else "none", **lnk)
         return y.view(*x.shape[:-1], N)
     y = torch.nn.functional.linear(x, weight.to(x.dtype))
     if bias is None and not gelu and residual is None:
