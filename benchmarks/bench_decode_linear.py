@@ -7,6 +7,7 @@ then `+ bias`, bias_gelu or the residual add as separate launches).
     python benchmarks/bench_decode_linear.py [--iters 50] [--reps 5]
     python benchmarks/bench_decode_linear.py --sweep   # kernel variants
     python benchmarks/bench_decode_linear.py --weight-dtype fp8 [--sweep]
+    python benchmarks/bench_decode_linear.py --weight-dtype mxfp4 [--sweep]
 
 Shapes: the four GPT-1.3B layer linears and the tied logits matrix
 (N 50304, K 2048), each at M = 1, 4 and 16. Device-event timing around one
@@ -26,6 +27,11 @@ e4m3 codes, one fp32 scale per output row) against the bf16 decode_linear on
 the same shapes, the two alternating in one process; its bytes are N*K + 4*N.
 With --sweep it sweeps the fp8 kernel's variants instead. --model 6.7B takes
 the GPT-6.7B shapes (hidden 4096).
+
+--weight-dtype mxfp4 times the MXFP4-weight kernel
+(csrc/decode_linear_mxfp4.hip: e2m1 codes, one e8m0 scale per 32 elements of
+K) against the fp8 kernel in the same way; its bytes are N*K/2 + N*K/32. With
+--sweep it sweeps the MXFP4 kernel's variants.
 
 --ln times the LayerNorm-prologue launch (ops.decode_linear(..., ln=...)) on
 the linears that follow a LayerNorm (qkv, ffn_up, logits) against the pair it
@@ -113,8 +119,10 @@ def main():
                         "host's launch rate (about 9 us per launch)")
     p.add_argument("--sweep", action="store_true",
                    help="time the kernel's (rows, waves, nt) variants")
-    p.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
-                   help="fp8: the fp8-weight kernel against the bf16 one")
+    p.add_argument("--weight-dtype", choices=("bf16", "fp8", "mxfp4"),
+                   default="bf16",
+                   help="fp8: the fp8-weight kernel against the bf16 one; "
+                        "mxfp4: the MXFP4-weight kernel against the fp8 one")
     p.add_argument("--ln", action="store_true",
                    help="one LN + linear launch against layernorm, then "
                         "decode_linear")
@@ -139,12 +147,14 @@ def main():
     fp8 = args.weight_dtype == "fp8"
     shapes = [sh for sh in layer_shapes(HIDDEN[args.model])
               if args.only is None or sh[0] in args.only]
+    if args.ln and args.weight_dtype == "mxfp4":
+        sys.exit("bench_decode_linear: no LayerNorm prologue for mxfp4")
     if args.ln:
         bench_ln(decode_linear, shapes, dev, args)
         return
-    if fp8:
+    if fp8 or args.weight_dtype == "mxfp4":
         from paddlefleetx_amd.ops import _reference as ref
-        bench_fp8(ext, ref, decode_linear, shapes, dev, args)
+        bench_fp8(ext, ref, decode_linear, shapes, dev, args, mx=not fp8)
         return
     if not args.sweep:
         print(f"{'linear':>9} {'N':>6} {'K':>5} {'M':>3} {'MiB':>7} | "
@@ -223,23 +233,32 @@ FP8_VARIANTS = [(rows, waves, nt) for rows in (8, 16, 32, 64)
                 for waves in (4, 8) for nt in (0, 1)]
 
 
-def bench_fp8(ext, ref, decode_linear, shapes, dev, args):
-    """fp8 weights against bf16 weights, one weight set = (bf16 W, codes,
-    scales); both kernels rotate over the same number of sets, sized so the
-    SMALLER (fp8) footprint still exceeds the Infinity Cache."""
+def bench_fp8(ext, ref, decode_linear, shapes, dev, args, mx=False):
+    """Quantised weights against the next wider storage: fp8 against bf16,
+    or (mx) MXFP4 against fp8. One weight set = (wide weight, wide scale,
+    codes, scales); both kernels rotate over the same number of sets, sized
+    so the SMALLER footprint still exceeds the Infinity Cache."""
     bf16 = torch.bfloat16
+    new, old = ("mxfp4", "fp8") if mx else ("fp8", "bf16")
+    kernel = ext.decode_linear_mxfp4 if mx else ext.decode_linear_fp8
+    twin = ref.decode_linear_mxfp4 if mx else ref.decode_linear_fp8
     if not args.sweep:
         print(f"{'linear':>9} {'N':>6} {'K':>5} {'M':>3} | "
-              f"{'fp8 us':>8} {'TB/s':>6} {'share':>6} | "
-              f"{'bf16 us':>8} {'TB/s':>6} {'share':>6} | bf16/fp8")
+              f"{new + ' us':>8} {'TB/s':>6} {'share':>6} | "
+              f"{old + ' us':>8} {'TB/s':>6} {'share':>6} | {old}/{new}")
     for name, N, K, ep in shapes:
         nb8, nb16 = N * K + 4 * N, N * K * 2
+        if mx:
+            nb8, nb16 = N * K // 2 + N * K // 32, nb8
         nsets = num_sets(nb8, args.max_sets)
         sets = []
         for _ in range(nsets):
             w = (torch.randn(N, K, device=dev) * 0.02).to(bf16)
-            codes, scale = ref.quantize_weight_rows(w)
-            sets.append((w, codes, scale))
+            if mx:
+                sets.append(ref.quantize_weight_rows(w)
+                            + ref.quantize_weight_mxfp4(w))
+            else:
+                sets.append((w, None) + ref.quantize_weight_rows(w))
         bias = torch.randn(N, device=dev).to(bf16)
         for M in args.ms:
             x = torch.randn(M, K, device=dev).to(bf16)
@@ -249,24 +268,22 @@ def bench_fp8(ext, ref, decode_linear, shapes, dev, args):
             act = "gelu" if ep == "bias_gelu" else None
 
             def run8(s):
-                return decode_linear(x, s[1], b, r, act, weight_scale=s[2])
+                return decode_linear(x, s[2], b, r, act, weight_scale=s[3])
 
             def run16(s):
-                return decode_linear(x, s[0], b, r, act)
+                return decode_linear(x, s[0], b, r, act, weight_scale=s[1])
 
             with torch.no_grad():
-                want = ref.decode_linear_fp8(x, sets[0][1], sets[0][2], b, r,
-                                             act).float()
+                want = twin(x, sets[0][2], sets[0][3], b, r, act).float()
                 err = (run8(sets[0]).float() - want).abs().max().item()
                 # two bf16 ulps of the largest value
                 assert err <= 2.0 ** -6 * want.abs().max().item(), \
-                    f"fp8 kernel and twin disagree: {err}"
+                    f"{new} kernel and twin disagree: {err}"
                 if args.sweep:
                     a = act or "none"
-                    fns = [(lambda s, v=v: ext.decode_linear_fp8(
-                        x, s[1], s[2], b, r, a, *v)) for v in FP8_VARIANTS]
-                    fns.append(lambda s: ext.decode_linear_fp8(
-                        x, s[1], s[2], b, r, a))
+                    fns = [(lambda s, v=v: kernel(
+                        x, s[2], s[3], b, r, a, *v)) for v in FP8_VARIANTS]
+                    fns.append(lambda s: kernel(x, s[2], s[3], b, r, a))
                     med, _ = alternate(fns, sets, args.iters, args.reps,
                                        not args.eager_launch)
                     best = min(range(len(FP8_VARIANTS)), key=lambda i: med[i])
@@ -285,8 +302,8 @@ def bench_fp8(ext, ref, decode_linear, shapes, dev, args):
                   f"{u8:8.2f} {g8:6.2f} {100 * g8 / HBM_MEASURED_TBS:5.1f}% | "
                   f"{u16:8.2f} {g16:6.2f} "
                   f"{100 * g16 / HBM_MEASURED_TBS:5.1f}% | "
-                  f"{u16 / u8:5.2f}x  (fp8 min/max {min(t8):.2f}/"
-                  f"{max(t8):.2f}, bf16 {min(t16):.2f}/{max(t16):.2f}; "
+                  f"{u16 / u8:5.2f}x  ({new} min/max {min(t8):.2f}/"
+                  f"{max(t8):.2f}, {old} {min(t16):.2f}/{max(t16):.2f}; "
                   f"worst pairing {min(t16) / max(t8):.2f}x)", flush=True)
         del sets
 

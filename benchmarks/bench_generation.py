@@ -7,7 +7,7 @@ Counterpart of the reference's inference latency harness
     python benchmarks/bench_generation.py [--model GPT-1.3B] \
         [--prompt-len 128] [--gen-len 64] \
         [--static-cache [--kv-dtype fp8] [--fused-sampling [--capture]] \
-         [--fused-linear [--weight-dtype fp8] [--fused-ln]]]
+         [--fused-linear [--weight-dtype fp8|mxfp4] [--fused-ln]]]
 """
 
 import argparse
@@ -51,10 +51,11 @@ def main():
                    help="decode-step linears and logits through "
                         "ops.decode_linear (Generation.fused_decode_linear); "
                         "needs --static-cache")
-    p.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+    p.add_argument("--weight-dtype", choices=("bf16", "fp8", "mxfp4"),
+                   default="bf16",
                    help="storage of the weights the fused decode linears "
-                        "stream (Generation.decode_weight_dtype); fp8 needs "
-                        "--fused-linear")
+                        "stream (Generation.decode_weight_dtype); fp8 and "
+                        "mxfp4 need --fused-linear")
     p.add_argument("--fused-ln", action="store_true",
                    help="ln1 / ln2 / final_ln of the decode step inside the "
                         "qkv / ffn_up / logits launches "
@@ -74,8 +75,8 @@ def main():
         p.error("--fused-linear needs --static-cache")
     if args.fused_ln and not args.fused_linear:
         p.error("--fused-ln needs --fused-linear")
-    if args.weight_dtype == "fp8" and not args.fused_linear:
-        p.error("--weight-dtype fp8 needs --fused-linear")
+    if args.weight_dtype != "bf16" and not args.fused_linear:
+        p.error(f"--weight-dtype {args.weight_dtype} needs --fused-linear")
 
     from paddlefleetx_amd.parallel.env import set_hcg
     from paddlefleetx_amd.parallel.topology import HybridTopology

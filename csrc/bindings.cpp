@@ -101,6 +101,13 @@ torch::Tensor decode_linear_fp8(torch::Tensor x, torch::Tensor wq,
                                 c10::optional<torch::Tensor> ln_weight,
                                 c10::optional<torch::Tensor> ln_bias,
                                 double ln_eps);
+// decode_linear_mxfp4.hip
+torch::Tensor decode_linear_mxfp4(torch::Tensor x, torch::Tensor wq,
+                                  torch::Tensor w_scale,
+                                  c10::optional<torch::Tensor> bias,
+                                  c10::optional<torch::Tensor> residual,
+                                  const std::string& act, long rows,
+                                  long waves, long nontemporal);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -201,6 +208,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
         py::arg("nontemporal") = -1, py::arg("ln_weight") = py::none(),
         py::arg("ln_bias") = py::none(), py::arg("ln_eps") = 1e-5);
+  m.def("decode_linear_mxfp4", &decode_linear_mxfp4,
+        "y = act(x D^T + bias) + residual for 1 <= M <= 16 bf16 rows, "
+        "K % 128 == 0: D is MXFP4, e2m1 codes wq uint8 [N, K/2] (even k in "
+        "the low nibble) and e8m0 scales w_scale uint8 [N, K/32], streamed "
+        "once and decoded exactly in registers, epilogue fused "
+        "(rows/waves/nontemporal: tuning overrides, default automatic)",
+        py::arg("x"), py::arg("wq"), py::arg("w_scale"),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(),
+        py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
+        py::arg("nontemporal") = -1);
   m.def("topp_select", &topp_select, "top-p nucleus cutoff + draw");
   m.def("sample_token", &sample_token,
         "logits row -> next token in one launch (min length, repetition "

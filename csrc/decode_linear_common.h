@@ -1,5 +1,6 @@
 // Pieces shared by the weight-streaming decode linears (decode_linear.hip:
-// bf16 weights, decode_linear_fp8.hip: fp8 codes plus a per-row scale): the
+// bf16 weights, decode_linear_fp8.hip: fp8 codes plus a per-row scale,
+// decode_linear_mxfp4.hip: MXFP4 codes plus a scale per 32 elements of K): the
 // 16-byte load and the fragment cast, the tanh-GELU, the per-element
 // epilogue, the launch arguments and every host-side check the two bindings
 // have in common. A fix applied to one copy of these alone would give wrong
@@ -30,7 +31,9 @@
 // row 0 as a valid base. The fragments of masked lanes need no zero either:
 // row n of C depends on row n of A alone and column m on column m of B
 // alone, and neither rows >= N nor columns >= M reach finish_element. They
-// start as zero and keep whatever they held.
+// start as zero and keep whatever they held. (decode_linear_mxfp4.hip sends
+// its masked lanes to a valid row another lane reads instead of predicating
+// them, for the sake of its counted waits; the reasoning above holds as is.)
 //
 // Everything sits in an unnamed namespace: each translation unit that
 // includes this header keeps its own copies.
@@ -280,7 +283,8 @@ struct Checked {
 
 // Everything that stands between raw pointers and a launch and is the same
 // for both bindings. op and wname are the binding's and its weight
-// argument's names, wdtype / kstep / rows_ok what its kernel takes.
+// argument's names, wdtype / kstep / rows_ok what its kernel takes, pack the
+// stored elements per entry of w (2 for 4-bit codes: w is [N, K / 2]).
 Checked check_decode_linear(const char* op, const char* wname,
                             const torch::Tensor& x, const torch::Tensor& w,
                             torch::ScalarType wdtype, int kstep,
@@ -291,7 +295,7 @@ Checked check_decode_linear(const char* op, const char* wname,
                             long nontemporal,
                             const c10::optional<torch::Tensor>& ln_weight,
                             const c10::optional<torch::Tensor>& ln_bias,
-                            double ln_eps) {
+                            double ln_eps, int pack = 1) {
   TORCH_CHECK(x.defined() && w.defined(), op, ": x and ", wname,
               " must be defined");
   TORCH_CHECK(x.is_cuda() && w.is_cuda(), op, ": x and ", wname,
@@ -307,8 +311,8 @@ Checked check_decode_linear(const char* op, const char* wname,
   TORCH_CHECK(x.is_contiguous(), op, ": x must be contiguous");
   TORCH_CHECK(w.is_contiguous(), op, ": ", wname, " must be contiguous");
   const long M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K, op, ": ", wname, " must be [N, ", K, "], got [",
-              N, ", ", w.size(1), "]");
+  TORCH_CHECK(w.size(1) * pack == K, op, ": ", wname, " must be [N, ",
+              K / pack, "], got [", N, ", ", w.size(1), "]");
   TORCH_CHECK(M >= 1 && M <= TILE, op, ": M must be in [1, 16], got ", M);
   TORCH_CHECK(K >= kstep && K % kstep == 0, op,
               ": K must be a positive multiple of ", kstep, ", got ", K);

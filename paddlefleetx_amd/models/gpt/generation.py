@@ -136,22 +136,24 @@ class GPTForGeneration(nn.Module):
                            "path")
             self.fused_decode_linear = False
         # storage of the weights a fused decode step streams: "bf16" (the
-        # parameters) or "fp8" (e4m3 codes + one fp32 scale per output row,
-        # quantised once, kept NEXT TO the bf16 parameters)
+        # parameters), "fp8" (e4m3 codes + one fp32 scale per output row) or
+        # "mxfp4" (e2m1 codes + one e8m0 scale per 32 elements of K);
+        # quantised once, kept NEXT TO the bf16 parameters
         self.decode_weight_dtype = str(cfg.get("decode_weight_dtype")
                                        or "bf16")
-        if self.decode_weight_dtype not in ("bf16", "fp8"):
+        if self.decode_weight_dtype not in ("bf16", "fp8", "mxfp4"):
             raise ValueError(
-                "Generation.decode_weight_dtype must be 'bf16' or 'fp8', got "
-                f"{self.decode_weight_dtype!r}")
-        if self.decode_weight_dtype == "fp8" and \
-                not cfg.get("fused_decode_linear", False):
+                "Generation.decode_weight_dtype must be 'bf16', 'fp8' or "
+                f"'mxfp4', got {self.decode_weight_dtype!r}")
+        quantised = self.decode_weight_dtype != "bf16"
+        if quantised and not cfg.get("fused_decode_linear", False):
             raise ValueError(
-                "Generation.decode_weight_dtype: fp8 needs "
-                "fused_decode_linear: true (only ops.decode_linear reads "
-                "fp8 weights)")
-        if self.decode_weight_dtype == "fp8" and not self.fused_decode_linear:
-            logger.warning("Generation.decode_weight_dtype: fp8 needs "
+                f"Generation.decode_weight_dtype: {self.decode_weight_dtype} "
+                "needs fused_decode_linear: true (only ops.decode_linear "
+                f"reads {self.decode_weight_dtype} weights)")
+        if quantised and not self.fused_decode_linear:
+            logger.warning("Generation.decode_weight_dtype: "
+                           f"{self.decode_weight_dtype} needs "
                            "model-parallel size 1: staying on bf16 weights")
             self.decode_weight_dtype = "bf16"
         # ln1 / ln2 / final_ln of a fused decode step inside the qkv / ffn_up
@@ -167,8 +169,8 @@ class GPTForGeneration(nn.Module):
                            "size 1: staying on separate LayerNorms")
             self.fused_decode_ln = False
         # a plain attribute, not a submodule: no state_dict entry, no cast
-        self._weight_codes = DecodeWeightCodes() \
-            if self.decode_weight_dtype == "fp8" else None
+        self._weight_codes = DecodeWeightCodes(self.decode_weight_dtype) \
+            if self.decode_weight_dtype != "bf16" else None
 
     def _decode_weights(self):
         """The weights a fused decode step streams: four linears per decoder

@@ -64,10 +64,13 @@ class StaticKVSlot:
 
 
 class DecodeWeightCodes:
-    """fp8 copies of decode-step weights (Generation.decode_weight_dtype:
-    fp8): per weight, e4m3 codes [N, K] and one fp32 scale per output row
-    (ref.quantize_weight_rows), N*K + 4*N bytes next to the bf16 parameter,
-    which stays (prefill, the embedding lookup and training read it).
+    """Quantised copies of decode-step weights (Generation.
+    decode_weight_dtype). "fp8" (the default): per weight, e4m3 codes [N, K]
+    and one fp32 scale per output row (ref.quantize_weight_rows), N*K + 4*N
+    bytes. "mxfp4": e2m1 codes uint8 [N, K/2] and e8m0 scales uint8
+    [N, K/32] (ref.quantize_weight_mxfp4; K % 32 == 0), N*K/2 + N*K/32
+    bytes. Either sits next to the bf16 parameter, which stays (prefill, the
+    embedding lookup and training read it).
 
     A plain object, not a module: the codes are no parameters or buffers, so
     they stay out of state_dict and .float() / .to(dtype) on the model never
@@ -78,7 +81,10 @@ class DecodeWeightCodes:
     capturing: refresh() before the capture (GPTForGeneration._start does).
     """
 
-    def __init__(self):
+    def __init__(self, fmt: str = "fp8"):
+        assert fmt in ("fp8", "mxfp4"), \
+            f"DecodeWeightCodes: format must be 'fp8' or 'mxfp4', got {fmt!r}"
+        self.format = fmt
         self._entries = {}
 
     def __len__(self) -> int:
@@ -86,8 +92,8 @@ class DecodeWeightCodes:
 
     @property
     def nbytes(self) -> int:
-        return sum(e[1].numel() + 4 * e[2].numel()
-                   for e in self._entries.values())
+        return sum(t.numel() * t.element_size()
+                   for e in self._entries.values() for t in e[1:3])
 
     @staticmethod
     def _stamp(w):
@@ -100,7 +106,10 @@ class DecodeWeightCodes:
                 "DecodeWeightCodes: a weight changed (or was first seen) "
                 "while a stream is capturing; call refresh() before capture")
         with torch.no_grad():
-            c, s = ref.quantize_weight_rows(w.detach())
+            if self.format == "mxfp4":
+                c, s = ref.quantize_weight_mxfp4(w.detach())
+            else:
+                c, s = ref.quantize_weight_rows(w.detach())
             codes.view(torch.uint8).copy_(c.view(torch.uint8))
             scale.copy_(s)
 
@@ -109,10 +118,16 @@ class DecodeWeightCodes:
         again, in place, whenever w's data_ptr or _version moved."""
         e = self._entries.get(id(w))
         if e is None or e[0] is not w or e[1].device != w.device:
-            codes = torch.empty(w.shape, dtype=torch.float8_e4m3fn,
-                                device=w.device)
-            scale = torch.empty(w.shape[0], dtype=torch.float32,
-                                device=w.device)
+            N, K = w.shape
+            if self.format == "mxfp4":
+                codes = torch.empty((N, K // 2), dtype=torch.uint8,
+                                    device=w.device)
+                scale = torch.empty((N, K // 32), dtype=torch.uint8,
+                                    device=w.device)
+            else:
+                codes = torch.empty(w.shape, dtype=torch.float8_e4m3fn,
+                                    device=w.device)
+                scale = torch.empty(N, dtype=torch.float32, device=w.device)
             e = self._entries[id(w)] = [w, codes, scale, None]
         if e[3] != self._stamp(w):
             self._quantize_into(w, e[1], e[2])

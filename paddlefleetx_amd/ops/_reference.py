@@ -265,6 +265,66 @@ def decode_linear_fp8(x: torch.Tensor, codes: torch.Tensor,
     return yf.to(x.dtype)
 
 
+MXFP4_BLOCK = 32  # elements along K that share one e8m0 scale
+# |value| of the e2m1 magnitude codes 0..7; bit 3 of a code is the sign
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_weight_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """OCP MXFP4 quantisation of a linear's weight: w [N, K], K % 32 == 0 ->
+    (codes uint8 [N, K/2], scale uint8 [N, K/32]). Element k of a row sits in
+    byte k/2, even k in the low nibble; scale byte e means 2^(e-127) for
+    elements [32j, 32j+32). fp32 arithmetic, every step exact in powers of
+    two (frexp / ldexp): per block amax = max|w|, 2^p the smallest power of
+    two with amax / 2^p <= 6 (p = 0 for an all-zero block), e = p + 127
+    clamped to [2, 252] so that every decoded value is a normal bf16;
+    code = e2m1_rne(clamp(w / 2^p, -6, 6)), ties to the even code."""
+    assert w.dim() == 2 and w.shape[1] % MXFP4_BLOCK == 0, \
+        f"quantize_weight_mxfp4: w must be [N, K], K % 32 == 0, got {tuple(w.shape)}"
+    N, K = w.shape
+    wf = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=-1)
+    m, ex = torch.frexp(amax)  # amax = m 2^ex, m in [0.5, 1); 6 = 0.75 2^3
+    p = torch.where(m <= 0.75, ex - 3, ex - 2)
+    p = torch.where(amax > 0, p, torch.zeros_like(p)).clamp(2 - 127, 252 - 127)
+    a = torch.ldexp(wf, -p[..., None]).clamp(-6.0, 6.0)
+    mag = a.abs()
+    # midpoints between neighbouring magnitudes; a tie goes to the even code
+    code = torch.zeros_like(mag, dtype=torch.uint8)
+    for mid, up in ((0.25, False), (0.75, True), (1.25, False), (1.75, True),
+                    (2.5, False), (3.5, True), (5.0, False)):
+        code += (mag >= mid if up else mag > mid).to(torch.uint8)
+    code = (code | ((a < 0).to(torch.uint8) << 3)).reshape(N, K)
+    packed = code[:, 0::2] | (code[:, 1::2] << 4)
+    return packed.contiguous(), (p + 127).to(torch.uint8)
+
+
+def dequantize_weight_mxfp4(codes: torch.Tensor, scale: torch.Tensor
+                            ) -> torch.Tensor:
+    """fp32 [N, K] = e2m1(nibble) * 2^(scale byte - 127), exact."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    nib = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(N, K).long()
+    table = torch.tensor(E2M1_VALUES, dtype=torch.float32,
+                         device=codes.device)
+    val = torch.where(nib >= 8, -table[nib & 7], table[nib & 7])
+    exp = scale.to(torch.int32).repeat_interleave(MXFP4_BLOCK, dim=1) - 127
+    return torch.ldexp(val, exp)
+
+
+def decode_linear_mxfp4(x: torch.Tensor, codes: torch.Tensor,
+                        w_scale: torch.Tensor,
+                        bias: Optional[torch.Tensor] = None,
+                        residual: Optional[torch.Tensor] = None,
+                        activation: Optional[str] = None,
+                        ln: Optional[tuple] = None) -> torch.Tensor:
+    """decode_linear over quantize_weight_mxfp4 codes, fp32 math from the
+    dequantised matrix D: y = act(x @ D^T + bias) + residual, one cast to
+    x.dtype. The scale is per 32 elements of K and part of D, so there is no
+    epilogue scale. ln as in decode_linear."""
+    return decode_linear(x, dequantize_weight_mxfp4(codes, w_scale), bias,
+                         residual, activation, ln)
+
+
 def decode_attention_fp8(qkv: torch.Tensor, k_cache: torch.Tensor,
                          v_cache: torch.Tensor, k_scale: torch.Tensor,
                          v_scale: torch.Tensor, seq_lens: torch.Tensor,

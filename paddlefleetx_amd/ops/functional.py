@@ -251,32 +251,39 @@ def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None,
                         ln=None) -> bool:
     """The contract of the decode_linear kernels (csrc/decode_linear.hip;
     csrc/decode_linear_fp8.hip when weight_scale is given: e4m3 weight, fp32
-    scale [N], K % 64 == 0 as a 16-byte load is 16 codes); straight-line, it
-    runs on every call of the eager decode loop."""
-    fp8 = weight_scale is not None
-    wdtype = torch.float8_e4m3fn if fp8 else torch.bfloat16
+    scale [N], K % 64 == 0 as a 16-byte load is 16 codes;
+    csrc/decode_linear_mxfp4.hip for a uint8 weight [N, K/2] with a uint8
+    scale [N, K/32], K % 128 == 0 as a 16-byte load is 32 codes);
+    straight-line, it runs on every call of the eager decode loop."""
+    mx = weight.dtype == torch.uint8
+    fp8 = weight_scale is not None and not mx
+    wdtype = torch.uint8 if mx else \
+        torch.float8_e4m3fn if fp8 else torch.bfloat16
     if not (use_hip(x2) and x2.dtype == torch.bfloat16
             and weight.dtype == wdtype and weight.dim() == 2):
         return False
     M, K = x2.shape
     N = weight.shape[0]
-    kstep = 64 if fp8 else 32
+    kstep = 128 if mx else 64 if fp8 else 32
     if not (1 <= M <= DECODE_LINEAR_MAX_M and K >= kstep and K % kstep == 0
-            and N >= 8 and N % 8 == 0 and weight.shape[1] == K):
+            and N >= 8 and N % 8 == 0
+            and weight.shape[1] * (2 if mx else 1) == K):
         return False
     grad = torch.is_grad_enabled()
-    for t in (x2, bias, residual) + (() if fp8 else (weight,)):
+    for t in (x2, bias, residual) + (() if fp8 or mx else (weight,)):
         if t is not None and (
                 t.dtype != torch.bfloat16 or t.device != x2.device
                 or not t.is_contiguous() or (grad and t.requires_grad)):
             return False
-    if fp8 and not (
+    if (fp8 or mx) and not (
             weight.device == x2.device and weight.is_contiguous()
-            and weight_scale.dtype == torch.float32
+            and weight_scale is not None
+            and weight_scale.dtype == (torch.uint8 if mx else torch.float32)
             and weight_scale.device == x2.device
-            and weight_scale.shape == (N,) and weight_scale.is_contiguous()):
+            and weight_scale.shape == ((N, K // 32) if mx else (N,))
+            and weight_scale.is_contiguous()):
         return False
-    if ln is not None and not _decode_linear_ln_fits(x2, ln):
+    if ln is not None and (mx or not _decode_linear_ln_fits(x2, ln)):
         return False
     return x2.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
 
@@ -303,6 +310,15 @@ def decode_linear(x, weight, bias=None, residual=None,
     act((x @ codes^T) * weight_scale + bias) + residual: weight-only fp8,
     bf16 activations. The fp8 kernel streams half the bytes and needs
     K % 64 == 0; what does not fit it computes ref.decode_linear_fp8.
+
+    A uint8 weight [N, K/2] holds MXFP4 codes (ref.quantize_weight_mxfp4:
+    two e2m1 codes per byte, even k in the low nibble) and needs weight_scale
+    uint8 [N, K/32], one e8m0 byte per 32 elements of K. The result is
+    act(x @ D^T + bias) + residual with D the dequantised matrix; the kernel
+    decodes D exactly in registers, streams N*K/2 + N*K/32 bytes and needs
+    K % 128 == 0; what does not fit it computes ref.decode_linear_mxfp4.
+    There is no LayerNorm prologue for these weights: with ln the op runs
+    layernorm first.
 
     ln = (ln_weight, ln_bias, eps) puts a LayerNorm in front:
     decode_linear(layernorm(x, ln_weight, ln_bias, eps), ...) with the same
@@ -333,6 +349,18 @@ def decode_linear(x, weight, bias=None, residual=None,
             return decode_linear(layernorm(x, g, b, eps), weight, bias,
                                  residual, activation, weight_scale)
         lnk = dict(ln_weight=g, ln_bias=b, ln_eps=float(eps))
+    if weight.dtype == torch.uint8:
+        if weight_scale is None or weight_scale.dtype != torch.uint8:
+            raise ValueError(
+                "decode_linear: a uint8 weight (MXFP4 codes) needs a uint8 "
+                "weight_scale [N, K/32]")
+        if _decode_linear_fits(x2, weight, bias, res2, weight_scale):
+            y = hip_ext().decode_linear_mxfp4(x2, weight, weight_scale, bias,
+                                              res2,
+                                              "gelu" if gelu else "none")
+            return y.view(*x.shape[:-1], N)
+        return ref.decode_linear_mxfp4(x, weight, weight_scale, bias,
+                                       residual, activation)
     if weight.dtype == torch.float8_e4m3fn:
         if weight_scale is None:
             raise ValueError(
