@@ -33,6 +33,15 @@ the GPT-6.7B shapes (hidden 4096).
 K) against the fp8 kernel in the same way; its bytes are N*K/2 + N*K/32. With
 --sweep it sweeps the MXFP4 kernel's variants.
 
+--wide times the kernel for batches of 17 to 64 rows
+(csrc/decode_linear_wide.hip, --weight-dtype bf16 or fp8, --ms default 32 64)
+against what the op computes for such a batch without that kernel
+(functional.DECODE_LINEAR_WIDE_MAX_M = 16): F.linear plus fp32 bias, GELU and
+residual passes with bf16 weights, ref.decode_linear_fp8 (the fp32 twin) with
+fp8 codes; the M <= 16 kernel on the first 16 rows alternates
+with them to show what the x stream and the extra MFMAs cost. With --sweep it
+sweeps the wide kernel's variants.
+
 --ln times the LayerNorm-prologue launch (ops.decode_linear(..., ln=...)) on
 the linears that follow a LayerNorm (qkv, ffn_up, logits) against the pair it
 replaces, layernorm then decode_linear, alternating in the same way; with
@@ -123,14 +132,20 @@ def main():
                    default="bf16",
                    help="fp8: the fp8-weight kernel against the bf16 one; "
                         "mxfp4: the MXFP4-weight kernel against the fp8 one")
+    p.add_argument("--wide", action="store_true",
+                   help="the 17 to 64 row kernel against the op's earlier "
+                        "path for such batches (bf16 or fp8 weights)")
     p.add_argument("--ln", action="store_true",
                    help="one LN + linear launch against layernorm, then "
                         "decode_linear")
     p.add_argument("--model", choices=sorted(HIDDEN), default="1.3B")
-    p.add_argument("--ms", type=int, nargs="+", default=list(MS))
+    p.add_argument("--ms", type=int, nargs="+", default=None,
+                   help="batch rows (default 1 4 16; 32 64 with --wide)")
     p.add_argument("--only", nargs="+", default=None,
                    help="names of the linears to run (default all)")
     args = p.parse_args()
+    if args.ms is None:
+        args.ms = [32, 64] if args.wide else list(MS)
     if not torch.cuda.is_available():
         sys.exit("bench_decode_linear: no GPU present (no CPU fallback)")
 
@@ -149,6 +164,12 @@ def main():
               if args.only is None or sh[0] in args.only]
     if args.ln and args.weight_dtype == "mxfp4":
         sys.exit("bench_decode_linear: no LayerNorm prologue for mxfp4")
+    if args.wide:
+        if args.ln or args.weight_dtype == "mxfp4":
+            sys.exit("bench_decode_linear: --wide takes bf16 or fp8 weights "
+                     "and no LayerNorm prologue")
+        bench_wide(ext, decode_linear, shapes, dev, args)
+        return
     if args.ln:
         bench_ln(decode_linear, shapes, dev, args)
         return
@@ -305,6 +326,88 @@ def bench_fp8(ext, ref, decode_linear, shapes, dev, args, mx=False):
                   f"{u16 / u8:5.2f}x  ({new} min/max {min(t8):.2f}/"
                   f"{max(t8):.2f}, {old} {min(t16):.2f}/{max(t16):.2f}; "
                   f"worst pairing {min(t16) / max(t8):.2f}x)", flush=True)
+        del sets
+
+
+def bench_wide(ext, decode_linear, shapes, dev, args):
+    """The 17 to 64 row kernel against the parent path of the same call and
+    against the M <= 16 kernel on the first 16 rows; one weight set =
+    (weight, scale or None)."""
+    from paddlefleetx_amd.ops import _reference as ref
+    from paddlefleetx_amd.ops import functional
+    wide_max = functional.DECODE_LINEAR_WIDE_MAX_M
+    bf16, fp8 = torch.bfloat16, args.weight_dtype == "fp8"
+    old = "twin" if fp8 else "eager"
+    if not args.sweep:
+        print(f"{'linear':>9} {'N':>6} {'K':>5} {'M':>3} | {'wide us':>8} "
+              f"{'TB/s':>6} {'share':>6} | {old + ' us':>9} | {'M=16 us':>8} "
+              f"| {old}/wide  wide/M=16")
+    for name, N, K, ep in shapes:
+        nbytes = N * K + 4 * N if fp8 else N * K * 2
+        nsets = num_sets(nbytes, args.max_sets)
+        sets = []
+        for _ in range(nsets):
+            w = (torch.randn(N, K, device=dev) * 0.02).to(bf16)
+            sets.append(ref.quantize_weight_rows(w) if fp8 else (w, None))
+        bias = torch.randn(N, device=dev).to(bf16)
+        for M in args.ms:
+            x = torch.randn(M, K, device=dev).to(bf16)
+            res = torch.randn(M, N, device=dev).to(bf16)
+            b = None if ep == "none" else bias
+            r = res if ep == "bias_res" else None
+            act = "gelu" if ep == "bias_gelu" else None
+            x16, r16 = x[:16], (r[:16] if r is not None else None)
+
+            def wide(s):
+                return decode_linear(x, s[0], b, r, act, weight_scale=s[1])
+
+            def narrow(s):
+                return decode_linear(x16, s[0], b, r16, act,
+                                     weight_scale=s[1])
+
+            def parent(s):
+                # the op with the wide kernel switched off; a captured graph
+                # keeps the path its capture took
+                functional.DECODE_LINEAR_WIDE_MAX_M = 16
+                try:
+                    return decode_linear(x, s[0], b, r, act,
+                                         weight_scale=s[1])
+                finally:
+                    functional.DECODE_LINEAR_WIDE_MAX_M = wide_max
+
+            with torch.no_grad():
+                want = parent(sets[0]).float()
+                err = (wide(sets[0]).float() - want).abs().max().item()
+                # two bf16 ulps of the largest value
+                assert err <= 2.0 ** -6 * want.abs().max().item(), \
+                    f"wide kernel and {old} disagree: {err}"
+                if args.sweep:
+                    a = act or "none"
+                    fns = [(lambda s, v=v: ext.decode_linear_wide(
+                        x, s[0], s[1], b, r, a, *v)) for v in FP8_VARIANTS]
+                    fns.append(lambda s: ext.decode_linear_wide(
+                        x, s[0], s[1], b, r, a))
+                    med, _ = alternate(fns, sets, args.iters, args.reps,
+                                       not args.eager_launch)
+                    best = min(range(len(FP8_VARIANTS)), key=lambda i: med[i])
+                    cells = " ".join(f"{v[0]}/{v[1]}/{v[2]}={u:.2f}"
+                                     for v, u in zip(FP8_VARIANTS, med))
+                    print(f"{name:>9} N={N} K={K} M={M}: auto={med[-1]:.2f} us"
+                          f" ({nbytes / med[-1] / 1e6:.2f} TB/s); best "
+                          f"rows/waves/nt={FP8_VARIANTS[best]} "
+                          f"{med[best]:.2f} us | {cells}", flush=True)
+                    continue
+                (uw, up, un), (tw, tp, _) = alternate(
+                    (wide, parent, narrow), sets, args.iters, args.reps,
+                    not args.eager_launch)
+            gw = nbytes / uw / 1e6  # TB/s
+            print(f"{name:>9} {N:6d} {K:5d} {M:3d} | {uw:8.2f} {gw:6.2f} "
+                  f"{100 * gw / HBM_MEASURED_TBS:5.1f}% | {up:9.2f} | "
+                  f"{un:8.2f} | {up / uw:6.2f}x {uw / un:6.2f}x  (wide "
+                  f"min/max {min(tw):.2f}/{max(tw):.2f}, {old} "
+                  f"{min(tp):.2f}/{max(tp):.2f}; worst pairing "
+                  f"{min(tp) / max(tw):.2f}x; max|diff| {err:.4f})",
+                  flush=True)
         del sets
 
 

@@ -7,11 +7,18 @@ Counterpart of the reference's inference latency harness
     python benchmarks/bench_generation.py [--model GPT-1.3B] \
         [--prompt-len 128] [--gen-len 64] \
         [--static-cache [--kv-dtype fp8] [--fused-sampling [--capture]] \
-         [--fused-linear [--weight-dtype fp8|mxfp4] [--fused-ln]]]
+         [--fused-linear [--weight-dtype fp8|mxfp4] [--fused-ln] \
+          [--no-wide-linear | --alternate-wide-linear]]]
+
+--no-wide-linear keeps batches of 17 to 64 off csrc/decode_linear_wide.hip
+(functional.DECODE_LINEAR_WIDE_MAX_M = 16: the library composition, or the
+fp32 twin with fp8 weights); --alternate-wide-linear times both settings in
+this process, generation by generation, on two generators over one model.
 """
 
 import argparse
 import os
+import statistics
 import sys
 import time
 
@@ -60,6 +67,12 @@ def main():
                    help="ln1 / ln2 / final_ln of the decode step inside the "
                         "qkv / ffn_up / logits launches "
                         "(Generation.fused_decode_ln); needs --fused-linear")
+    p.add_argument("--no-wide-linear", action="store_true",
+                   help="batches of 17 to 64 fall back as they did before "
+                        "the wide decode_linear kernel")
+    p.add_argument("--alternate-wide-linear", action="store_true",
+                   help="time every batch with and without the wide kernel, "
+                        "alternating")
     p.add_argument("--finish-check-interval", type=int, default=None,
                    help="Generation.finish_check_interval (fused sampling)")
     p.add_argument("--fixed-capacity", action="store_true",
@@ -91,11 +104,17 @@ def main():
     shape = SHAPES[args.model]
     vocab = 50304
     max_len = args.prompt_len + args.gen_len + 8
+    from paddlefleetx_amd.ops import functional
+    wide_max = functional.DECODE_LINEAR_WIDE_MAX_M
+    # (label, DECODE_LINEAR_WIDE_MAX_M) of every generator that is timed
+    modes = [("", 16 if args.no_wide_linear else wide_max)]
+    if args.alternate_wide_linear:
+        modes = [("no wide ", 16), ("wide    ", wide_max)]
     torch.manual_seed(0)
     with torch.device(dev):
         gpt = GPTModel(vocab_size=vocab, max_position_embeddings=max_len,
                        dtype=dtype, **shape)
-        model = GPTForGeneration(gpt, {
+        models = [GPTForGeneration(gpt, {
             "max_dec_len": args.gen_len,
             "decoding_strategy": "sampling",
             "top_p": args.top_p,
@@ -112,8 +131,7 @@ def main():
                if args.finish_check_interval else {}),
             **({"kv_cache_capacity": args.prompt_len + args.gen_len}
                if args.fixed_capacity else {}),
-        })
-    model.eval()
+        }).eval() for _ in modes]
 
     print(f"# decode bench {args.model} prompt={args.prompt_len} "
           f"gen={args.gen_len} top_p={args.top_p} "
@@ -121,26 +139,38 @@ def main():
           f"fused_sampling={args.fused_sampling} capture={args.capture} "
           f"fused_linear={args.fused_linear} "
           f"weight_dtype={args.weight_dtype} fused_ln={args.fused_ln} "
-          f"({dev})")
+          f"wide_linear={[m for _, m in modes]} ({dev})")
+
+    def generate(i, ids):
+        # a captured step keeps the path of the call that captured it
+        functional.DECODE_LINEAR_WIDE_MAX_M = modes[i][1]
+        out = models[i](ids)
+        if dev == "cuda":
+            torch.cuda.synchronize()
+        return out
+
     for bs in [int(b) for b in args.batches.split(",")]:
         ids = torch.randint(0, vocab - 2, (bs, args.prompt_len), device=dev)
+        reps = 3
+        dts = [[] for _ in modes]
         with torch.no_grad():
-            model(ids)  # warmup (compile caches, allocator)
-            if dev == "cuda":
-                torch.cuda.synchronize()
-            t0 = time.time()
-            reps = 3
+            for i in range(len(modes)):
+                generate(i, ids)  # warmup (compile caches, allocator)
             for _ in range(reps):
-                out = model(ids)
-            if dev == "cuda":
-                torch.cuda.synchronize()
-        dt = (time.time() - t0) / reps
-        # GPTForGeneration returns only the GENERATED ids
-        ntok = out.shape[1] if out.shape[1] <= args.gen_len \
-            else out.shape[1] - args.prompt_len
-        ms_tok = dt * 1000.0 / max(1, ntok)
-        print(f"bs={bs:3d}: {dt*1000:8.1f} ms/gen ({ntok} new tok) = "
-              f"{ms_tok:7.2f} ms/token, {bs*ntok/dt:8.0f} tok/s")
+                for i in range(len(modes)):
+                    t0 = time.time()
+                    out = generate(i, ids)
+                    dts[i].append(time.time() - t0)
+        for (label, _), t in zip(modes, dts):
+            dt = statistics.median(t) if len(modes) > 1 else sum(t) / reps
+            # GPTForGeneration returns only the GENERATED ids
+            ntok = out.shape[1] if out.shape[1] <= args.gen_len \
+                else out.shape[1] - args.prompt_len
+            ms_tok = dt * 1000.0 / max(1, ntok)
+            print(f"{label}bs={bs:3d}: {dt*1000:8.1f} ms/gen ({ntok} new "
+                  f"tok) = {ms_tok:7.2f} ms/token, {bs*ntok/dt:8.0f} tok/s"
+                  + (f"  (min/max {min(t)*1000:.1f}/{max(t)*1000:.1f} ms)"
+                     if len(modes) > 1 else ""), flush=True)
 
 
 if __name__ == "__main__":

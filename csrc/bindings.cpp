@@ -108,6 +108,13 @@ torch::Tensor decode_linear_mxfp4(torch::Tensor x, torch::Tensor wq,
                                   c10::optional<torch::Tensor> residual,
                                   const std::string& act, long rows,
                                   long waves, long nontemporal);
+// decode_linear_wide.hip
+torch::Tensor decode_linear_wide(torch::Tensor x, torch::Tensor weight,
+                                 c10::optional<torch::Tensor> w_scale,
+                                 c10::optional<torch::Tensor> bias,
+                                 c10::optional<torch::Tensor> residual,
+                                 const std::string& act, long rows, long waves,
+                                 long nontemporal);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -215,6 +222,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "once and decoded exactly in registers, epilogue fused "
         "(rows/waves/nontemporal: tuning overrides, default automatic)",
         py::arg("x"), py::arg("wq"), py::arg("w_scale"),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(),
+        py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
+        py::arg("nontemporal") = -1);
+  m.def("decode_linear_wide", &decode_linear_wide,
+        "y = act((x W^T) (* w_scale) + bias) + residual for 17 <= M <= 64 "
+        "bf16 rows: weight bf16 [N, K] (K % 32 == 0), or float8_e4m3fn codes "
+        "[N, K] with w_scale fp32 [N] (K % 64 == 0), streamed once, 2 to 4 "
+        "MFMA column tiles per weight fragment, epilogue fused "
+        "(rows/waves/nontemporal: tuning overrides, default automatic)",
+        py::arg("x"), py::arg("weight"), py::arg("w_scale") = py::none(),
         py::arg("bias") = py::none(), py::arg("residual") = py::none(),
         py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
         py::arg("nontemporal") = -1);

@@ -284,7 +284,8 @@ struct Checked {
 // Everything that stands between raw pointers and a launch and is the same
 // for both bindings. op and wname are the binding's and its weight
 // argument's names, wdtype / kstep / rows_ok what its kernel takes, pack the
-// stored elements per entry of w (2 for 4-bit codes: w is [N, K / 2]).
+// stored elements per entry of w (2 for 4-bit codes: w is [N, K / 2]),
+// [m_lo, m_hi] the batch rows it serves (decode_linear_wide.hip: 17 to 64).
 Checked check_decode_linear(const char* op, const char* wname,
                             const torch::Tensor& x, const torch::Tensor& w,
                             torch::ScalarType wdtype, int kstep,
@@ -295,7 +296,8 @@ Checked check_decode_linear(const char* op, const char* wname,
                             long nontemporal,
                             const c10::optional<torch::Tensor>& ln_weight,
                             const c10::optional<torch::Tensor>& ln_bias,
-                            double ln_eps, int pack = 1) {
+                            double ln_eps, int pack = 1, long m_lo = 1,
+                            long m_hi = TILE) {
   TORCH_CHECK(x.defined() && w.defined(), op, ": x and ", wname,
               " must be defined");
   TORCH_CHECK(x.is_cuda() && w.is_cuda(), op, ": x and ", wname,
@@ -313,7 +315,8 @@ Checked check_decode_linear(const char* op, const char* wname,
   const long M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) * pack == K, op, ": ", wname, " must be [N, ",
               K / pack, "], got [", N, ", ", w.size(1), "]");
-  TORCH_CHECK(M >= 1 && M <= TILE, op, ": M must be in [1, 16], got ", M);
+  TORCH_CHECK(M >= m_lo && M <= m_hi, op, ": M must be in [", m_lo, ", ", m_hi,
+              "], got ", M);
   TORCH_CHECK(K >= kstep && K % kstep == 0, op,
               ": K must be a positive multiple of ", kstep, ", got ", K);
   TORCH_CHECK(N >= 8 && N % 8 == 0, op,

@@ -223,10 +223,12 @@ def bias_gelu(x, bias=None):
 
 
 # ---------------------------------------------------------------------------
-# Weight-streaming linear for the decode step (M <= 16 rows)
+# Weight-streaming linear for the decode step (M <= 16 rows; 17 to 64 rows
+# with bf16 or fp8 weights: csrc/decode_linear_wide.hip)
 # ---------------------------------------------------------------------------
 
 DECODE_LINEAR_MAX_M = 16
+DECODE_LINEAR_WIDE_MAX_M = 64  # 16 switches the wide kernel off
 DECODE_LINEAR_LN_MAX_K = 7168  # LN_MAX_K of csrc/decode_linear_common.h
 
 
@@ -253,7 +255,9 @@ def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None,
     csrc/decode_linear_fp8.hip when weight_scale is given: e4m3 weight, fp32
     scale [N], K % 64 == 0 as a 16-byte load is 16 codes;
     csrc/decode_linear_mxfp4.hip for a uint8 weight [N, K/2] with a uint8
-    scale [N, K/32], K % 128 == 0 as a 16-byte load is 32 codes);
+    scale [N, K/32], K % 128 == 0 as a 16-byte load is 32 codes;
+    csrc/decode_linear_wide.hip for 16 < M <= DECODE_LINEAR_WIDE_MAX_M with
+    bf16 or fp8 weights and no ln);
     straight-line, it runs on every call of the eager decode loop."""
     mx = weight.dtype == torch.uint8
     fp8 = weight_scale is not None and not mx
@@ -265,7 +269,9 @@ def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None,
     M, K = x2.shape
     N = weight.shape[0]
     kstep = 128 if mx else 64 if fp8 else 32
-    if not (1 <= M <= DECODE_LINEAR_MAX_M and K >= kstep and K % kstep == 0
+    max_m = DECODE_LINEAR_MAX_M if mx or ln is not None else \
+        max(DECODE_LINEAR_MAX_M, DECODE_LINEAR_WIDE_MAX_M)
+    if not (1 <= M <= max_m and K >= kstep and K % kstep == 0
             and N >= 8 and N % 8 == 0
             and weight.shape[1] * (2 if mx else 1) == K):
         return False
@@ -302,8 +308,17 @@ def decode_linear(x, weight, bias=None, residual=None,
     contiguous on one device, run the HIP kernel (an error if the extension
     is missing): the weight is streamed once, the sum is kept in fp32
     through the epilogue and rounded to bf16 once. Every other case (CPU,
-    fp32, M > 16, other K or N, strided operands, a tensor that requires
+    fp32, M > 64, other K or N, strided operands, a tensor that requires
     grad with grad enabled) computes the same expression from library ops.
+
+    17 <= M <= DECODE_LINEAR_WIDE_MAX_M (64) under the same contract runs
+    csrc/decode_linear_wide.hip: the same single launch and single
+    rounding, 2 to 4 MFMA column tiles per weight fragment. With fp8 codes
+    always; with bf16 weights where it was measured not slower than the
+    library composition (csrc/KERNELS.md): K <= 4096 and a GELU or a
+    residual, or a bias alone up to M = 48. A bare matmul (the logits) and
+    K > 4096 stay on the library GEMM. MXFP4 weights at M > 16 compute the
+    twin, and with ln the op runs layernorm first, then this op without ln.
 
     A float8_e4m3fn weight (ref.quantize_weight_rows codes) needs
     weight_scale [N] fp32, one scale per output row, and gives
@@ -366,6 +381,11 @@ def decode_linear(x, weight, bias=None, residual=None,
             raise ValueError(
                 "decode_linear: a float8_e4m3fn weight needs weight_scale")
         if _decode_linear_fits(x2, weight, bias, res2, weight_scale):
+            if x2.shape[0] > DECODE_LINEAR_MAX_M:
+                y = hip_ext().decode_linear_wide(
+                    x2, weight, weight_scale, bias, res2,
+                    "gelu" if gelu else "none")
+                return y.view(*x.shape[:-1], N)
             y = hip_ext().decode_linear_fp8(x2, weight, weight_scale, bias,
                                             res2, "gelu" if gelu else "none",
                                             **lnk)
@@ -376,7 +396,19 @@ def decode_linear(x, weight, bias=None, residual=None,
         raise ValueError(
             "decode_linear: weight_scale goes with a float8_e4m3fn weight, "
             f"got {weight.dtype}")
-    if _decode_linear_fits(x2, weight, bias, res2):
+    M = x2.shape[0]
+    # Measured (csrc/KERNELS.md): past 16 rows the library GEMM is the faster
+    # matmul; the wide kernel pays where its epilogue replaces the fp32
+    # passes below, up to K = 4096, and past 48 rows only for GELU or a
+    # residual.
+    wide_pays = M <= DECODE_LINEAR_MAX_M or (
+        K <= 4096 and (gelu or residual is not None
+                       or (bias is not None and M <= 48)))
+    if wide_pays and _decode_linear_fits(x2, weight, bias, res2):
+        if M > DECODE_LINEAR_MAX_M:
+            y = hip_ext().decode_linear_wide(x2, weight, None, bias, res2,
+                                             "gelu" if gelu else "none")
+            return y.view(*x.shape[:-1], N)
         y = hip_ext().decode_linear(x2, weight, bias, res2,
                                     "gelu" if gelu else "none", **lnk)
         return y.view(*x.shape[:-1], N)

@@ -29,7 +29,8 @@ hip_sources = [
     for s in ("bindings.cpp", "layernorm.hip", "elementwise.hip",
               "softmax.hip", "attention.hip", "decode_attention.hip",
               "decode_attention_fp8.hip", "decode_linear.hip",
-              "decode_linear_fp8.hip", "decode_linear_mxfp4.hip", "topp.hip",
+              "decode_linear_fp8.hip", "decode_linear_mxfp4.hip",
+              "decode_linear_wide.hip", "topp.hip",
               "sample_token.hip", "moe.hip", "mfma_probe.hip")
 ]
 
