@@ -40,7 +40,10 @@ against what the op computes for such a batch without that kernel
 residual passes with bf16 weights, ref.decode_linear_fp8 (the fp32 twin) with
 fp8 codes; the M <= 16 kernel on the first 16 rows alternates
 with them to show what the x stream and the extra MFMAs cost. With --sweep it
-sweeps the wide kernel's variants.
+sweeps the wide kernel's variants. --wide --weight-dtype mxfp4 times
+csrc/decode_linear_wide_mxfp4.hip against the op with the wide path off (the
+fp32 twin) and against the fp8 wide kernel, the three alternating; its
+--sweep rows are rows per wave.
 
 --ln times the LayerNorm-prologue launch (ops.decode_linear(..., ln=...)) on
 the linears that follow a LayerNorm (qkv, ffn_up, logits) against the pair it
@@ -165,10 +168,13 @@ def main():
     if args.ln and args.weight_dtype == "mxfp4":
         sys.exit("bench_decode_linear: no LayerNorm prologue for mxfp4")
     if args.wide:
-        if args.ln or args.weight_dtype == "mxfp4":
-            sys.exit("bench_decode_linear: --wide takes bf16 or fp8 weights "
-                     "and no LayerNorm prologue")
-        bench_wide(ext, decode_linear, shapes, dev, args)
+        if args.ln:
+            sys.exit("bench_decode_linear: --wide takes no LayerNorm "
+                     "prologue")
+        if args.weight_dtype == "mxfp4":
+            bench_wide_mxfp4(ext, decode_linear, shapes, dev, args)
+        else:
+            bench_wide(ext, decode_linear, shapes, dev, args)
         return
     if args.ln:
         bench_ln(decode_linear, shapes, dev, args)
@@ -407,6 +413,89 @@ def bench_wide(ext, decode_linear, shapes, dev, args):
                   f"min/max {min(tw):.2f}/{max(tw):.2f}, {old} "
                   f"{min(tp):.2f}/{max(tp):.2f}; worst pairing "
                   f"{min(tp) / max(tw):.2f}x; max|diff| {err:.4f})",
+                  flush=True)
+        del sets
+
+
+def bench_wide_mxfp4(ext, decode_linear, shapes, dev, args):
+    """The 17 to 64 row MXFP4 kernel (csrc/decode_linear_wide_mxfp4.hip)
+    against the op with the wide path switched off (the fp32 twin) and
+    against the fp8 wide kernel on the same matrix; one weight set = (fp8
+    codes, fp8 scales, MXFP4 codes, MXFP4 scales). The sweep's rows are rows
+    per WAVE: a workgroup serves waves * rows of them."""
+    from paddlefleetx_amd.ops import _reference as ref
+    from paddlefleetx_amd.ops import functional
+    wide_max = functional.DECODE_LINEAR_WIDE_MAX_M
+    bf16 = torch.bfloat16
+    if not args.sweep:
+        print(f"{'linear':>9} {'N':>6} {'K':>5} {'M':>3} | {'mxfp4 us':>8} "
+              f"{'TB/s':>6} {'share':>6} | {'twin us':>9} | {'fp8 us':>8} "
+              f"| twin/mxfp4  fp8/mxfp4")
+    for name, N, K, ep in shapes:
+        nbytes = N * K // 2 + N * K // 32
+        nsets = num_sets(nbytes, args.max_sets)
+        sets = []
+        for _ in range(nsets):
+            w = (torch.randn(N, K, device=dev) * 0.02).to(bf16)
+            sets.append(ref.quantize_weight_rows(w)
+                        + ref.quantize_weight_mxfp4(w))
+        bias = torch.randn(N, device=dev).to(bf16)
+        for M in args.ms:
+            x = torch.randn(M, K, device=dev).to(bf16)
+            res = torch.randn(M, N, device=dev).to(bf16)
+            b = None if ep == "none" else bias
+            r = res if ep == "bias_res" else None
+            act = "gelu" if ep == "bias_gelu" else None
+
+            def wide(s):
+                return decode_linear(x, s[2], b, r, act, weight_scale=s[3])
+
+            def fp8(s):
+                return decode_linear(x, s[0], b, r, act, weight_scale=s[1])
+
+            def parent(s):
+                # the op with the wide kernels switched off; a captured graph
+                # keeps the path its capture took
+                functional.DECODE_LINEAR_WIDE_MAX_M = 16
+                try:
+                    return decode_linear(x, s[2], b, r, act,
+                                         weight_scale=s[3])
+                finally:
+                    functional.DECODE_LINEAR_WIDE_MAX_M = wide_max
+
+            with torch.no_grad():
+                want = parent(sets[0]).float()
+                err = (wide(sets[0]).float() - want).abs().max().item()
+                # two bf16 ulps of the largest value
+                assert err <= 2.0 ** -6 * want.abs().max().item(), \
+                    f"wide mxfp4 kernel and twin disagree: {err}"
+                if args.sweep:
+                    a = act or "none"
+                    fns = [(lambda s, v=v: ext.decode_linear_wide_mxfp4(
+                        x, s[2], s[3], b, r, a, *v)) for v in FP8_VARIANTS]
+                    fns.append(lambda s: ext.decode_linear_wide_mxfp4(
+                        x, s[2], s[3], b, r, a))
+                    med, _ = alternate(fns, sets, args.iters, args.reps,
+                                       not args.eager_launch)
+                    best = min(range(len(FP8_VARIANTS)), key=lambda i: med[i])
+                    cells = " ".join(f"{v[0]}/{v[1]}/{v[2]}={u:.2f}"
+                                     for v, u in zip(FP8_VARIANTS, med))
+                    print(f"{name:>9} N={N} K={K} M={M}: auto={med[-1]:.2f} us"
+                          f" ({nbytes / med[-1] / 1e6:.2f} TB/s); best "
+                          f"rows/waves/nt={FP8_VARIANTS[best]} "
+                          f"{med[best]:.2f} us | {cells}", flush=True)
+                    continue
+                (uw, up, u8), (tw, tp, t8) = alternate(
+                    (wide, parent, fp8), sets, args.iters, args.reps,
+                    not args.eager_launch)
+            gw = nbytes / uw / 1e6  # TB/s
+            print(f"{name:>9} {N:6d} {K:5d} {M:3d} | {uw:8.2f} {gw:6.2f} "
+                  f"{100 * gw / HBM_MEASURED_TBS:5.1f}% | {up:9.2f} | "
+                  f"{u8:8.2f} | {up / uw:6.2f}x {u8 / uw:6.2f}x  (mxfp4 "
+                  f"min/max {min(tw):.2f}/{max(tw):.2f}, twin "
+                  f"{min(tp):.2f}/{max(tp):.2f}, fp8 {min(t8):.2f}/"
+                  f"{max(t8):.2f}; worst pairings {min(tp) / max(tw):.2f}x "
+                  f"{min(t8) / max(tw):.2f}x; max|diff| {err:.4f})",
                   flush=True)
         del sets
 

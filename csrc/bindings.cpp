@@ -115,6 +115,13 @@ torch::Tensor decode_linear_wide(torch::Tensor x, torch::Tensor weight,
                                  c10::optional<torch::Tensor> residual,
                                  const std::string& act, long rows, long waves,
                                  long nontemporal);
+// decode_linear_wide_mxfp4.hip
+torch::Tensor decode_linear_wide_mxfp4(torch::Tensor x, torch::Tensor wq,
+                                       torch::Tensor w_scale,
+                                       c10::optional<torch::Tensor> bias,
+                                       c10::optional<torch::Tensor> residual,
+                                       const std::string& act, long rows,
+                                       long waves, long nontemporal);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -232,6 +239,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MFMA column tiles per weight fragment, epilogue fused "
         "(rows/waves/nontemporal: tuning overrides, default automatic)",
         py::arg("x"), py::arg("weight"), py::arg("w_scale") = py::none(),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(),
+        py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
+        py::arg("nontemporal") = -1);
+  m.def("decode_linear_wide_mxfp4", &decode_linear_wide_mxfp4,
+        "y = act(x D^T + bias) + residual for 17 <= M <= 64 bf16 rows, "
+        "K % 128 == 0, K >= 512: D is MXFP4 (wq uint8 [N, K/2], w_scale uint8 "
+        "[N, K/32], the layout of decode_linear_mxfp4), codes streamed once, "
+        "x shared by the workgroup through a double-buffered LDS slab, waves "
+        "split rows, epilogue fused (rows: weight rows per wave, 8, 16, 32 "
+        "or 64; waves 4 or 8; nontemporal 0 or 1; default automatic)",
+        py::arg("x"), py::arg("wq"), py::arg("w_scale"),
         py::arg("bias") = py::none(), py::arg("residual") = py::none(),
         py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
         py::arg("nontemporal") = -1);

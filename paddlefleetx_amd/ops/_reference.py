@@ -303,10 +303,15 @@ def dequantize_weight_mxfp4(codes: torch.Tensor, scale: torch.Tensor
                             ) -> torch.Tensor:
     """fp32 [N, K] = e2m1(nibble) * 2^(scale byte - 127), exact."""
     N, K = codes.shape[0], codes.shape[1] * 2
-    nib = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(N, K).long()
-    table = torch.tensor(E2M1_VALUES, dtype=torch.float32,
-                         device=codes.device)
-    val = torch.where(nib >= 8, -table[nib & 7], table[nib & 7])
+    nib = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(N, K)
+    nib = nib.to(torch.int32)
+    # E2M1_VALUES[m] from the bits of m = (exponent << 1 | mantissa), with no
+    # table on the device: a host-to-device copy cannot be captured into a
+    # graph, and this twin serves captured decode steps
+    half = (nib & 1).float() * 0.5
+    ex = (nib >> 1) & 3
+    mag = torch.where(ex == 0, half, torch.ldexp(1.0 + half, ex - 1))
+    val = torch.where(nib >= 8, -mag, mag)
     exp = scale.to(torch.int32).repeat_interleave(MXFP4_BLOCK, dim=1) - 127
     return torch.ldexp(val, exp)
 

@@ -224,7 +224,8 @@ def bias_gelu(x, bias=None):
 
 # ---------------------------------------------------------------------------
 # Weight-streaming linear for the decode step (M <= 16 rows; 17 to 64 rows
-# with bf16 or fp8 weights: csrc/decode_linear_wide.hip)
+# with bf16 or fp8 weights: csrc/decode_linear_wide.hip, with MXFP4 weights:
+# csrc/decode_linear_wide_mxfp4.hip)
 # ---------------------------------------------------------------------------
 
 DECODE_LINEAR_MAX_M = 16
@@ -257,7 +258,8 @@ def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None,
     csrc/decode_linear_mxfp4.hip for a uint8 weight [N, K/2] with a uint8
     scale [N, K/32], K % 128 == 0 as a 16-byte load is 32 codes;
     csrc/decode_linear_wide.hip for 16 < M <= DECODE_LINEAR_WIDE_MAX_M with
-    bf16 or fp8 weights and no ln);
+    bf16 or fp8 weights and no ln, csrc/decode_linear_wide_mxfp4.hip for the
+    same M with MXFP4 weights, K >= 512 and no ln);
     straight-line, it runs on every call of the eager decode loop."""
     mx = weight.dtype == torch.uint8
     fp8 = weight_scale is not None and not mx
@@ -269,7 +271,8 @@ def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None,
     M, K = x2.shape
     N = weight.shape[0]
     kstep = 128 if mx else 64 if fp8 else 32
-    max_m = DECODE_LINEAR_MAX_M if mx or ln is not None else \
+    # the wide MXFP4 kernel's rings want four k-steps: K >= 512
+    max_m = DECODE_LINEAR_MAX_M if ln is not None or (mx and K < 512) else \
         max(DECODE_LINEAR_MAX_M, DECODE_LINEAR_WIDE_MAX_M)
     if not (1 <= M <= max_m and K >= kstep and K % kstep == 0
             and N >= 8 and N % 8 == 0
@@ -317,8 +320,10 @@ def decode_linear(x, weight, bias=None, residual=None,
     always; with bf16 weights where it was measured not slower than the
     library composition (csrc/KERNELS.md): K <= 4096 and a GELU or a
     residual, or a bias alone up to M = 48. A bare matmul (the logits) and
-    K > 4096 stay on the library GEMM. MXFP4 weights at M > 16 compute the
-    twin, and with ln the op runs layernorm first, then this op without ln.
+    K > 4096 stay on the library GEMM. MXFP4 weights at these M run
+    csrc/decode_linear_wide_mxfp4.hip (x shared by the workgroup through an
+    LDS slab) when K >= 512 and compute the twin below that. With ln the op
+    runs layernorm first, then this op without ln.
 
     A float8_e4m3fn weight (ref.quantize_weight_rows codes) needs
     weight_scale [N] fp32, one scale per output row, and gives
@@ -370,9 +375,11 @@ def decode_linear(x, weight, bias=None, residual=None,
                 "decode_linear: a uint8 weight (MXFP4 codes) needs a uint8 "
                 "weight_scale [N, K/32]")
         if _decode_linear_fits(x2, weight, bias, res2, weight_scale):
-            y = hip_ext().decode_linear_mxfp4(x2, weight, weight_scale, bias,
-                                              res2,
-                                              "gelu" if gelu else "none")
+            kernel = hip_ext().decode_linear_wide_mxfp4 \
+                if x2.shape[0] > DECODE_LINEAR_MAX_M \
+                else hip_ext().decode_linear_mxfp4
+            y = kernel(x2, weight, weight_scale, bias, res2,
+                       "gelu" if gelu else "none")
             return y.view(*x.shape[:-1], N)
         return ref.decode_linear_mxfp4(x, weight, weight_scale, bias,
                                        residual, activation)

@@ -30,7 +30,8 @@ hip_sources = [
               "softmax.hip", "attention.hip", "decode_attention.hip",
               "decode_attention_fp8.hip", "decode_linear.hip",
               "decode_linear_fp8.hip", "decode_linear_mxfp4.hip",
-              "decode_linear_wide.hip", "topp.hip",
+              "decode_linear_wide.hip", "decode_linear_wide_mxfp4.hip",
+              "topp.hip",
               "sample_token.hip", "moe.hip", "mfma_probe.hip")
 ]
 
