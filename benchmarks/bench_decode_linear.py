@@ -45,6 +45,13 @@ csrc/decode_linear_wide_mxfp4.hip against the op with the wide path off (the
 fp32 twin) and against the fp8 wide kernel, the three alternating; its
 --sweep rows are rows per wave.
 
+--codes times the tiled GEMM that reads codes (csrc/linear_codes.hip, M >= 65,
+--weight-dtype fp8 or mxfp4, --ms default 128 256 2048) against the op with
+functional.LINEAR_CODES = False (the fp32 twin, the path before that kernel)
+and against F.linear on the bf16 weights plus the eager epilogue (the library
+GEMM), the three alternating; it prints the achieved share of the bf16 MFMA
+peak and of the HBM rate. With --sweep it sweeps the workgroup tile's N.
+
 --ln times the LayerNorm-prologue launch (ops.decode_linear(..., ln=...)) on
 the linears that follow a LayerNorm (qkv, ffn_up, logits) against the pair it
 replaces, layernorm then decode_linear, alternating in the same way; with
@@ -138,6 +145,9 @@ def main():
     p.add_argument("--wide", action="store_true",
                    help="the 17 to 64 row kernel against the op's earlier "
                         "path for such batches (bf16 or fp8 weights)")
+    p.add_argument("--codes", action="store_true",
+                   help="the M >= 65 tiled GEMM over fp8 / mxfp4 codes "
+                        "against the twin and the library GEMM")
     p.add_argument("--ln", action="store_true",
                    help="one LN + linear launch against layernorm, then "
                         "decode_linear")
@@ -148,7 +158,8 @@ def main():
                    help="names of the linears to run (default all)")
     args = p.parse_args()
     if args.ms is None:
-        args.ms = [32, 64] if args.wide else list(MS)
+        args.ms = [128, 256, 2048] if args.codes else \
+            [32, 64] if args.wide else list(MS)
     if not torch.cuda.is_available():
         sys.exit("bench_decode_linear: no GPU present (no CPU fallback)")
 
@@ -167,6 +178,12 @@ def main():
               if args.only is None or sh[0] in args.only]
     if args.ln and args.weight_dtype == "mxfp4":
         sys.exit("bench_decode_linear: no LayerNorm prologue for mxfp4")
+    if args.codes:
+        if args.ln or args.wide or args.weight_dtype == "bf16":
+            sys.exit("bench_decode_linear: --codes takes --weight-dtype fp8 "
+                     "or mxfp4 and neither --ln nor --wide")
+        bench_codes(ext, decode_linear, bias_gelu, shapes, dev, args)
+        return
     if args.wide:
         if args.ln:
             sys.exit("bench_decode_linear: --wide takes no LayerNorm "
@@ -496,6 +513,96 @@ def bench_wide_mxfp4(ext, decode_linear, shapes, dev, args):
                   f"{min(tp):.2f}/{max(tp):.2f}, fp8 {min(t8):.2f}/"
                   f"{max(t8):.2f}; worst pairings {min(tp) / max(tw):.2f}x "
                   f"{min(t8) / max(tw):.2f}x; max|diff| {err:.4f})",
+                  flush=True)
+        del sets
+
+
+MFMA_PEAK_TFLOPS = 2500.0  # MI355X dense bf16 matrix peak (2.5 PF/s)
+CODES_TILES = (128, 64, 32)
+
+
+def bench_codes(ext, decode_linear, bias_gelu, shapes, dev, args):
+    """csrc/linear_codes.hip against the op with LINEAR_CODES off (the fp32
+    twin) and against the library GEMM on the bf16 weights; one weight set =
+    (bf16 weight, codes, scales)."""
+    from paddlefleetx_amd.ops import _reference as ref
+    from paddlefleetx_amd.ops import functional
+    bf16, mx = torch.bfloat16, args.weight_dtype == "mxfp4"
+    quant = ref.quantize_weight_mxfp4 if mx else ref.quantize_weight_rows
+    if not args.sweep:
+        print(f"{'linear':>9} {'N':>6} {'K':>5} {'M':>5} | {'codes us':>9} "
+              f"{'%MFMA':>6} {'%HBM':>6} | {'twin us':>10} | {'lib us':>9} | "
+              f"twin/codes  lib/codes")
+    for name, N, K, ep in shapes:
+        wbytes = N * K // 2 + N * K // 32 if mx else N * K + 4 * N
+        nsets = num_sets(wbytes, min(args.max_sets, 4))
+        sets = []
+        for _ in range(nsets):
+            w = (torch.randn(N, K, device=dev) * 0.02).to(bf16)
+            sets.append((w,) + quant(w))
+        bias = torch.randn(N, device=dev).to(bf16)
+        for M in args.ms:
+            x = torch.randn(M, K, device=dev).to(bf16)
+            res = torch.randn(M, N, device=dev).to(bf16)
+            b = None if ep == "none" else bias
+            r = res if ep == "bias_res" else None
+            act = "gelu" if ep == "bias_gelu" else None
+
+            def codes(s):
+                return decode_linear(x, s[1], b, r, act, weight_scale=s[2])
+
+            def twin(s):
+                # the op with the kernel switched off; a captured graph keeps
+                # the path its capture took
+                functional.LINEAR_CODES = False
+                try:
+                    return decode_linear(x, s[1], b, r, act,
+                                         weight_scale=s[2])
+                finally:
+                    functional.LINEAR_CODES = True
+
+            def lib(s):
+                if ep == "none":
+                    return torch.matmul(x, s[0].t())
+                if ep == "bias":
+                    return F.linear(x, s[0], b)
+                if ep == "bias_gelu":
+                    return bias_gelu(F.linear(x, s[0]), b)
+                return res + (F.linear(x, s[0]) + b)
+
+            with torch.no_grad():
+                want = twin(sets[0]).float()
+                err = (codes(sets[0]).float() - want).abs().max().item()
+                # two bf16 ulps of the largest value
+                assert err <= 2.0 ** -6 * want.abs().max().item(), \
+                    f"linear_codes and twin disagree: {err}"
+                if args.sweep:
+                    a = act or "none"
+                    fns = [(lambda s, t=t: ext.linear_codes(
+                        x, s[1], s[2], b, r, a, t)) for t in CODES_TILES]
+                    fns.append(lambda s: ext.linear_codes(x, s[1], s[2], b, r,
+                                                          a))
+                    med, _ = alternate(fns, sets, args.iters, args.reps,
+                                       not args.eager_launch)
+                    cells = " ".join(f"tile_n={t}: {u:.2f}"
+                                     for t, u in zip(CODES_TILES, med))
+                    print(f"{name:>9} N={N} K={K} M={M}: auto={med[-1]:.2f} us"
+                          f" | {cells}", flush=True)
+                    continue
+                (uc, ut, ul), (tc, tt, tl) = alternate(
+                    (codes, twin, lib), sets, args.iters, args.reps,
+                    not args.eager_launch)
+            flops = 2.0 * M * N * K
+            nbytes = wbytes + 2 * M * K + 2 * M * N * (2 if r is not None
+                                                       else 1)
+            print(f"{name:>9} {N:6d} {K:5d} {M:5d} | {uc:9.2f} "
+                  f"{100 * flops / uc / 1e6 / MFMA_PEAK_TFLOPS:5.1f}% "
+                  f"{100 * nbytes / uc / 1e6 / HBM_MEASURED_TBS:5.1f}% | "
+                  f"{ut:10.2f} | {ul:9.2f} | {ut / uc:6.2f}x {ul / uc:6.2f}x  "
+                  f"(codes min/max {min(tc):.2f}/{max(tc):.2f}, twin "
+                  f"{min(tt):.2f}/{max(tt):.2f}, lib {min(tl):.2f}/"
+                  f"{max(tl):.2f}; worst pairings {min(tt) / max(tc):.2f}x "
+                  f"{min(tl) / max(tc):.2f}x; max|diff| {err:.4f})",
                   flush=True)
         del sets
 

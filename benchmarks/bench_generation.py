@@ -73,6 +73,10 @@ def main():
     p.add_argument("--alternate-wide-linear", action="store_true",
                    help="time every batch with and without the wide kernel, "
                         "alternating")
+    p.add_argument("--alternate-linear-codes", action="store_true",
+                   help="time every batch with functional.LINEAR_CODES off "
+                        "and on, alternating (batches of 65 and more with "
+                        "fp8 or mxfp4 weights: csrc/linear_codes.hip)")
     p.add_argument("--finish-check-interval", type=int, default=None,
                    help="Generation.finish_check_interval (fused sampling)")
     p.add_argument("--fixed-capacity", action="store_true",
@@ -106,10 +110,14 @@ def main():
     max_len = args.prompt_len + args.gen_len + 8
     from paddlefleetx_amd.ops import functional
     wide_max = functional.DECODE_LINEAR_WIDE_MAX_M
-    # (label, DECODE_LINEAR_WIDE_MAX_M) of every generator that is timed
-    modes = [("", 16 if args.no_wide_linear else wide_max)]
+    # (label, DECODE_LINEAR_WIDE_MAX_M, LINEAR_CODES) of every generator
+    # that is timed
+    modes = [("", 16 if args.no_wide_linear else wide_max, True)]
     if args.alternate_wide_linear:
-        modes = [("no wide ", 16), ("wide    ", wide_max)]
+        modes = [("no wide ", 16, True), ("wide    ", wide_max, True)]
+    if args.alternate_linear_codes:
+        modes = [("no codes ", modes[0][1], False),
+                 ("codes    ", modes[0][1], True)]
     torch.manual_seed(0)
     with torch.device(dev):
         gpt = GPTModel(vocab_size=vocab, max_position_embeddings=max_len,
@@ -139,11 +147,13 @@ def main():
           f"fused_sampling={args.fused_sampling} capture={args.capture} "
           f"fused_linear={args.fused_linear} "
           f"weight_dtype={args.weight_dtype} fused_ln={args.fused_ln} "
-          f"wide_linear={[m for _, m in modes]} ({dev})")
+          f"wide_linear={[m[1] for m in modes]} "
+          f"linear_codes={[m[2] for m in modes]} ({dev})")
 
     def generate(i, ids):
         # a captured step keeps the path of the call that captured it
         functional.DECODE_LINEAR_WIDE_MAX_M = modes[i][1]
+        functional.LINEAR_CODES = modes[i][2]
         out = models[i](ids)
         if dev == "cuda":
             torch.cuda.synchronize()
@@ -161,7 +171,7 @@ def main():
                     t0 = time.time()
                     out = generate(i, ids)
                     dts[i].append(time.time() - t0)
-        for (label, _), t in zip(modes, dts):
+        for (label, _, _), t in zip(modes, dts):
             dt = statistics.median(t) if len(modes) > 1 else sum(t) / reps
             # GPTForGeneration returns only the GENERATED ids
             ntok = out.shape[1] if out.shape[1] <= args.gen_len \

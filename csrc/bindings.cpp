@@ -122,6 +122,12 @@ torch::Tensor decode_linear_wide_mxfp4(torch::Tensor x, torch::Tensor wq,
                                        c10::optional<torch::Tensor> residual,
                                        const std::string& act, long rows,
                                        long waves, long nontemporal);
+// linear_codes.hip
+torch::Tensor linear_codes(torch::Tensor x, torch::Tensor codes,
+                           torch::Tensor w_scale,
+                           c10::optional<torch::Tensor> bias,
+                           c10::optional<torch::Tensor> residual,
+                           const std::string& act, long tile_n);
 // topp.hip
 std::vector<torch::Tensor> topp_select(torch::Tensor sorted_p,
                                        torch::Tensor sorted_idx,
@@ -253,6 +259,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none(), py::arg("residual") = py::none(),
         py::arg("act") = "none", py::arg("rows") = 0, py::arg("waves") = 0,
         py::arg("nontemporal") = -1);
+  m.def("linear_codes", &linear_codes,
+        "y = act((x W^T) (* w_scale) + bias) + residual for M >= 65 bf16 "
+        "rows, a tiled GEMM that reads weight codes: float8_e4m3fn [N, K] "
+        "with w_scale fp32 [N] (K % 64 == 0), or MXFP4 uint8 [N, K/2] with "
+        "w_scale uint8 [N, K/32] (K % 128 == 0); codes decoded once per "
+        "workgroup tile into a double-buffered LDS slab, epilogue fused "
+        "(tile_n: N per workgroup tile, 32, 64 or 128; 0 automatic)",
+        py::arg("x"), py::arg("codes"), py::arg("w_scale"),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(),
+        py::arg("act") = "none", py::arg("tile_n") = 0);
   m.def("topp_select", &topp_select, "top-p nucleus cutoff + draw");
   m.def("sample_token", &sample_token,
         "logits row -> next token in one launch (min length, repetition "

@@ -225,12 +225,16 @@ def bias_gelu(x, bias=None):
 # ---------------------------------------------------------------------------
 # Weight-streaming linear for the decode step (M <= 16 rows; 17 to 64 rows
 # with bf16 or fp8 weights: csrc/decode_linear_wide.hip, with MXFP4 weights:
-# csrc/decode_linear_wide_mxfp4.hip)
+# csrc/decode_linear_wide_mxfp4.hip; 65 rows and more with fp8 or MXFP4
+# weights: csrc/linear_codes.hip, a tiled GEMM that reads the codes)
 # ---------------------------------------------------------------------------
 
 DECODE_LINEAR_MAX_M = 16
 DECODE_LINEAR_WIDE_MAX_M = 64  # 16 switches the wide kernel off
 DECODE_LINEAR_LN_MAX_K = 7168  # LN_MAX_K of csrc/decode_linear_common.h
+LINEAR_CODES = True  # False: fp8 / MXFP4 weights at M >= 65 compute the twin
+LINEAR_CODES_MIN_M = 65  # the first row count past the wide kernels
+LINEAR_CODES_MIN_N = 128  # below, a workgroup tile is mostly masked
 
 
 def _decode_linear_ln_fits(x2, ln) -> bool:
@@ -259,7 +263,9 @@ def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None,
     scale [N, K/32], K % 128 == 0 as a 16-byte load is 32 codes;
     csrc/decode_linear_wide.hip for 16 < M <= DECODE_LINEAR_WIDE_MAX_M with
     bf16 or fp8 weights and no ln, csrc/decode_linear_wide_mxfp4.hip for the
-    same M with MXFP4 weights, K >= 512 and no ln);
+    same M with MXFP4 weights, K >= 512 and no ln; csrc/linear_codes.hip for
+    M >= LINEAR_CODES_MIN_M with fp8 or MXFP4 weights, N >= LINEAR_CODES_MIN_N
+    and no ln);
     straight-line, it runs on every call of the eager decode loop."""
     mx = weight.dtype == torch.uint8
     fp8 = weight_scale is not None and not mx
@@ -274,7 +280,9 @@ def _decode_linear_fits(x2, weight, bias, residual, weight_scale=None,
     # the wide MXFP4 kernel's rings want four k-steps: K >= 512
     max_m = DECODE_LINEAR_MAX_M if ln is not None or (mx and K < 512) else \
         max(DECODE_LINEAR_MAX_M, DECODE_LINEAR_WIDE_MAX_M)
-    if not (1 <= M <= max_m and K >= kstep and K % kstep == 0
+    tiled = (LINEAR_CODES and (fp8 or mx) and ln is None
+             and M >= LINEAR_CODES_MIN_M and N >= LINEAR_CODES_MIN_N)
+    if not ((1 <= M <= max_m or tiled) and K >= kstep and K % kstep == 0
             and N >= 8 and N % 8 == 0
             and weight.shape[1] * (2 if mx else 1) == K):
         return False
@@ -324,6 +332,14 @@ def decode_linear(x, weight, bias=None, residual=None,
     csrc/decode_linear_wide_mxfp4.hip (x shared by the workgroup through an
     LDS slab) when K >= 512 and compute the twin below that. With ln the op
     runs layernorm first, then this op without ln.
+
+    M >= 65 with fp8 or MXFP4 weights and N >= LINEAR_CODES_MIN_N (128) runs
+    csrc/linear_codes.hip under the same contract: a tiled GEMM that reads
+    the stored codes, decodes each once per workgroup tile into LDS and
+    keeps the single launch and the single rounding. Narrower N, and
+    everything with LINEAR_CODES = False, computes the twin. bf16 weights
+    at these M stay on the library GEMM. With ln the op runs layernorm
+    first, as at 17 to 64 rows.
 
     A float8_e4m3fn weight (ref.quantize_weight_rows codes) needs
     weight_scale [N] fp32, one scale per output row, and gives
@@ -375,9 +391,10 @@ def decode_linear(x, weight, bias=None, residual=None,
                 "decode_linear: a uint8 weight (MXFP4 codes) needs a uint8 "
                 "weight_scale [N, K/32]")
         if _decode_linear_fits(x2, weight, bias, res2, weight_scale):
-            kernel = hip_ext().decode_linear_wide_mxfp4 \
-                if x2.shape[0] > DECODE_LINEAR_MAX_M \
-                else hip_ext().decode_linear_mxfp4
+            M = x2.shape[0]
+            kernel = hip_ext().linear_codes if M >= LINEAR_CODES_MIN_M \
+                else hip_ext().decode_linear_wide_mxfp4 \
+                if M > DECODE_LINEAR_MAX_M else hip_ext().decode_linear_mxfp4
             y = kernel(x2, weight, weight_scale, bias, res2,
                        "gelu" if gelu else "none")
             return y.view(*x.shape[:-1], N)
@@ -388,6 +405,10 @@ def decode_linear(x, weight, bias=None, residual=None,
             raise ValueError(
                 "decode_linear: a float8_e4m3fn weight needs weight_scale")
         if _decode_linear_fits(x2, weight, bias, res2, weight_scale):
+            if x2.shape[0] >= LINEAR_CODES_MIN_M:
+                y = hip_ext().linear_codes(x2, weight, weight_scale, bias,
+                                           res2, "gelu" if gelu else "none")
+                return y.view(*x.shape[:-1], N)
             if x2.shape[0] > DECODE_LINEAR_MAX_M:
                 y = hip_ext().decode_linear_wide(
                     x2, weight, weight_scale, bias, res2,

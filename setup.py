@@ -31,7 +31,7 @@ hip_sources = [
               "decode_attention_fp8.hip", "decode_linear.hip",
               "decode_linear_fp8.hip", "decode_linear_mxfp4.hip",
               "decode_linear_wide.hip", "decode_linear_wide_mxfp4.hip",
-              "topp.hip",
+              "linear_codes.hip", "topp.hip",
               "sample_token.hip", "moe.hip", "mfma_probe.hip")
 ]
 
