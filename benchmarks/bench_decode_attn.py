@@ -6,10 +6,17 @@ transpose/reshape).
 
     python benchmarks/bench_decode_attn.py [--iters 50] [--reps 5]
     python benchmarks/bench_decode_attn.py --kv-dtype fp8
+    python benchmarks/bench_decode_attn.py --shared 16 [--splits 0,4,8]
 
 With --kv-dtype fp8 the two variants are the bf16-cache kernel and the
 fp8-cache kernel (csrc/decode_attention_fp8.hip, e4m3 codes + one fp32 scale
 per cached row) on the same data; fp8 bytes are 2*B*h*(L+1)*(D+4).
+
+With --shared G the two variants are decode_attention on the EXPANDED cache
+(16 rows, each with its own copy of its prompt's K/V) and
+decode_attention_shared (csrc/decode_attention_shared.hip) on P = 16/G prompts
+stored once, 8 own tokens per row; effective bytes are what each variant has
+to read. --splits lists forced prefix chunk counts to time (0 = the rule).
 
 Device-event timing, warm-up, the two variants alternate inside one process
 and the median over the repetitions is reported. Bytes are the K/V the
@@ -65,6 +72,11 @@ def main():
     p.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
                    help="bf16: fused bf16 kernel vs the tuple-cache "
                         "composition; fp8: bf16 kernel vs fp8 kernel")
+    p.add_argument("--shared", type=int, default=0, metavar="G",
+                   help="expanded-cache kernel vs the shared-prompt op, 16 "
+                        "rows as 16/G prompts x G samples")
+    p.add_argument("--splits", default="0",
+                   help="with --shared: prefix chunk counts, comma separated")
     args = p.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_decode_attn: no GPU present (no CPU fallback)")
@@ -74,6 +86,8 @@ def main():
     hip_ext()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if args.shared:
+        return sweep_shared(args, dev)
     if args.kv_dtype == "fp8":
         return sweep_fp8(args, dev)
     print(f"# decode attention microbench on {torch.cuda.get_device_name(0)}; "
@@ -186,6 +200,71 @@ def sweep_fp8(args, dev):
               f"(bf16 min/max {min(t_b):.2f}/{max(t_b):.2f}, fp8 "
               f"{min(t_f):.2f}/{max(t_f):.2f}; max|diff| {err:.4f})")
         del sets_b, sets_f
+
+
+def sweep_shared(args, dev):
+    """decode_attention on the expanded cache vs decode_attention_shared,
+    alternating; each variant rotates over its own buffer sets."""
+    from paddlefleetx_amd.ops import decode_attention, decode_attention_shared
+    G, B, h, D, own = args.shared, 16, 16, 128, 8
+    assert B % G == 0, "--shared G must divide 16"
+    P = B // G
+    splits = [int(x) for x in args.splits.split(",")]
+    print(f"# decode attention, expanded vs shared prompt (G={G}, P={P}), on "
+          f"{torch.cuda.get_device_name(0)}; iters={args.iters} "
+          f"reps={args.reps}; h={h} D={D}, {own} own tokens per row; bytes "
+          f"expanded = 2*B*h*(L+own+1)*D*2, shared = 2*h*(P*L+B*(own+1))*D*2")
+    print(f"{'G':>3} {'L':>5} {'chunks':>6} | {'MiB':>7} {'expand us':>9} "
+          f"{'GB/s':>8} | {'MiB':>7} {'shared us':>9} {'GB/s':>8} | "
+          f"expand/shared")
+    scale = 1.0 / math.sqrt(D)
+    for L in (128, 2048):
+        ne = 2 * B * h * (L + own + 1) * D * 2
+        ns = 2 * h * (P * L + B * (own + 1)) * D * 2
+        sets_e, sets_s = [], []
+        for i in range(num_sets(ne, args.max_sets)):
+            qkv = torch.randn(B, 1, h, 3, D, device=dev).to(torch.bfloat16)
+            kp = torch.randn(P, h, L, D, device=dev).to(torch.bfloat16)
+            vp = torch.randn(P, h, L, D, device=dev).to(torch.bfloat16)
+            kc = torch.randn(B, h, own + 1, D, device=dev).to(torch.bfloat16)
+            vc = torch.randn(B, h, own + 1, D, device=dev).to(torch.bfloat16)
+            ke = torch.cat((kp.repeat_interleave(G, 0), kc), 2).contiguous()
+            ve = torch.cat((vp.repeat_interleave(G, 0), vc), 2).contiguous()
+            sets_e.append((qkv, ke, ve))
+            if i < num_sets(ns, args.max_sets):
+                sets_s.append((qkv, kp, vp, kc, vc))
+        lens = torch.full((B,), L + own, dtype=torch.int32, device=dev)
+        plens = torch.full((P,), L, dtype=torch.int32, device=dev)
+
+        def expanded(s):
+            return decode_attention(s[0], s[1], s[2], lens, scale=scale,
+                                    max_seq_len=L + own + 1)
+
+        for ns_ in splits:
+            def shared(s):
+                return decode_attention_shared(
+                    s[0], s[1], s[2], plens, s[3], s[4], lens, G, scale=scale,
+                    max_prefix_len=L, num_splits=ns_)
+
+            with torch.no_grad():
+                a = expanded(sets_e[0]).float()
+                b = shared(sets_s[0]).float()
+                err = (a - b).abs().max().item()
+                assert err < 3e-2, f"variants disagree: {err}"
+                time_block(expanded, sets_e, args.iters)  # warm-up
+                time_block(shared, sets_s, args.iters)
+                t_e, t_s = [], []
+                for _ in range(args.reps):
+                    t_e.append(time_block(expanded, sets_e, args.iters))
+                    t_s.append(time_block(shared, sets_s, args.iters))
+            ue, us = statistics.median(t_e), statistics.median(t_s)
+            print(f"{G:3d} {L:5d} {ns_:6d} | {len(sets_e) * ne / 2**20:7.1f} "
+                  f"{ue:9.2f} {ne / ue / 1e3:8.1f} | "
+                  f"{len(sets_s) * ns / 2**20:7.1f} {us:9.2f} "
+                  f"{ns / us / 1e3:8.1f} | {ue / us:5.2f}x  (expand min/max "
+                  f"{min(t_e):.2f}/{max(t_e):.2f}, shared {min(t_s):.2f}/"
+                  f"{max(t_s):.2f}; max|diff| {err:.4f})")
+        del sets_e, sets_s
 
 
 if __name__ == "__main__":

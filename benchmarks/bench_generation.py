@@ -77,6 +77,14 @@ def main():
                    help="time every batch with functional.LINEAR_CODES off "
                         "and on, alternating (batches of 65 and more with "
                         "fp8 or mxfp4 weights: csrc/linear_codes.hip)")
+    p.add_argument("--num-return-sequences", type=int, default=1, metavar="G",
+                   help="Generation.num_return_sequences: every batch row is "
+                        "a prompt that is sampled G times (bs*G rows run)")
+    p.add_argument("--shared-prompt", action="store_true",
+                   help="time Generation.shared_prompt_cache off against on, "
+                        "alternating in one process (needs --static-cache "
+                        "--fused-sampling and G >= 2); also prints the time "
+                        "of prefill + first token and the cache bytes")
     p.add_argument("--finish-check-interval", type=int, default=None,
                    help="Generation.finish_check_interval (fused sampling)")
     p.add_argument("--fixed-capacity", action="store_true",
@@ -94,6 +102,10 @@ def main():
         p.error("--fused-ln needs --fused-linear")
     if args.weight_dtype != "bf16" and not args.fused_linear:
         p.error(f"--weight-dtype {args.weight_dtype} needs --fused-linear")
+
+    if args.shared_prompt and (args.alternate_wide_linear
+                               or args.alternate_linear_codes):
+        p.error("--shared-prompt is an alternation of its own")
 
     from paddlefleetx_amd.parallel.env import set_hcg
     from paddlefleetx_amd.parallel.topology import HybridTopology
@@ -118,12 +130,18 @@ def main():
     if args.alternate_linear_codes:
         modes = [("no codes ", modes[0][1], False),
                  ("codes    ", modes[0][1], True)]
+    modes = [m + (False,) for m in modes]
+    if args.shared_prompt:
+        modes = [("unshared ",) + modes[0][1:3] + (False,),
+                 ("shared   ",) + modes[0][1:3] + (True,)]
     torch.manual_seed(0)
     with torch.device(dev):
         gpt = GPTModel(vocab_size=vocab, max_position_embeddings=max_len,
                        dtype=dtype, **shape)
         models = [GPTForGeneration(gpt, {
-            "max_dec_len": args.gen_len,
+            "max_dec_len": gen_len,
+            "num_return_sequences": args.num_return_sequences,
+            "shared_prompt_cache": m[3],
             "decoding_strategy": "sampling",
             "top_p": args.top_p,
             "use_topp_sampling": True,
@@ -139,7 +157,12 @@ def main():
                if args.finish_check_interval else {}),
             **({"kv_cache_capacity": args.prompt_len + args.gen_len}
                if args.fixed_capacity else {}),
-        }).eval() for _ in modes]
+        }).eval() for m in modes
+            for gen_len in ((args.gen_len, 1) if args.shared_prompt
+                            else (args.gen_len,))]
+    # with --shared-prompt every mode also has a max_dec_len = 1 twin: its
+    # call is the prefill plus the first token
+    stride = 2 if args.shared_prompt else 1
 
     print(f"# decode bench {args.model} prompt={args.prompt_len} "
           f"gen={args.gen_len} top_p={args.top_p} "
@@ -154,10 +177,20 @@ def main():
         # a captured step keeps the path of the call that captured it
         functional.DECODE_LINEAR_WIDE_MAX_M = modes[i][1]
         functional.LINEAR_CODES = modes[i][2]
-        out = models[i](ids)
+        out = models[i * stride](ids)
         if dev == "cuda":
             torch.cuda.synchronize()
         return out
+
+    def prefill_ms(i, ids):
+        ts = []
+        for _ in range(4):  # the first call warms up
+            t0 = time.time()
+            models[i * stride + 1](ids)
+            if dev == "cuda":
+                torch.cuda.synchronize()
+            ts.append((time.time() - t0) * 1000.0)
+        return statistics.median(ts[1:])
 
     for bs in [int(b) for b in args.batches.split(",")]:
         ids = torch.randint(0, vocab - 2, (bs, args.prompt_len), device=dev)
@@ -171,16 +204,24 @@ def main():
                     t0 = time.time()
                     out = generate(i, ids)
                     dts[i].append(time.time() - t0)
-        for (label, _, _), t in zip(modes, dts):
+        for i, ((label, _, _, _), t) in enumerate(zip(modes, dts)):
             dt = statistics.median(t) if len(modes) > 1 else sum(t) / reps
             # GPTForGeneration returns only the GENERATED ids
             ntok = out.shape[1] if out.shape[1] <= args.gen_len \
                 else out.shape[1] - args.prompt_len
             ms_tok = dt * 1000.0 / max(1, ntok)
+            rows = bs * out.shape[0] // ids.shape[0]
+            extra = ""
+            if args.shared_prompt:
+                with torch.no_grad():
+                    extra = f"  prefill+1 {prefill_ms(i, ids):.1f} ms"
+                st = models[i * stride]._graph_state
+                if st is not None:
+                    extra += f"  cache {st['cache'].nbytes / 2**20:.1f} MiB"
             print(f"{label}bs={bs:3d}: {dt*1000:8.1f} ms/gen ({ntok} new "
-                  f"tok) = {ms_tok:7.2f} ms/token, {bs*ntok/dt:8.0f} tok/s"
+                  f"tok) = {ms_tok:7.2f} ms/token, {rows*ntok/dt:8.0f} tok/s"
                   + (f"  (min/max {min(t)*1000:.1f}/{max(t)*1000:.1f} ms)"
-                     if len(modes) > 1 else ""), flush=True)
+                     if len(modes) > 1 else "") + extra, flush=True)
 
 
 if __name__ == "__main__":

@@ -73,6 +73,14 @@ torch::Tensor attn_bwd_packed(torch::Tensor dout, torch::Tensor qkv,
 torch::Tensor decode_attn(torch::Tensor qkv, torch::Tensor k_cache,
                           torch::Tensor v_cache, torch::Tensor seq_lens,
                           double scale, long max_seq_len, long num_splits);
+// decode_attention_shared.hip
+torch::Tensor decode_attn_shared(torch::Tensor qkv, torch::Tensor k_prefix,
+                                 torch::Tensor v_prefix,
+                                 torch::Tensor prefix_lens,
+                                 torch::Tensor k_cache, torch::Tensor v_cache,
+                                 torch::Tensor seq_lens, long group,
+                                 double scale, long max_prefix_len,
+                                 long num_splits);
 // decode_attention_fp8.hip
 torch::Tensor decode_attn_fp8(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor k_scale,
@@ -196,6 +204,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("seq_lens"), py::arg("scale"), py::arg("max_seq_len"),
         py::arg("num_splits") = 0);
+  m.def("decode_attn_shared", &decode_attn_shared,
+        "decode_attn for B = P * group rows grouped by prompt: each prompt's "
+        "K/V prefix [P, h, Lcap, D] is stored and read once for its group "
+        "(MFMA), every row's own tokens live in k_cache/v_cache [B, h, Scap, "
+        "D]; seq_lens is the total length per row, the append goes to "
+        "position seq_lens[b] - prefix_lens[b / group] of the row's cache "
+        "(num_splits: prefix chunks, 0 automatic)",
+        py::arg("qkv"), py::arg("k_prefix"), py::arg("v_prefix"),
+        py::arg("prefix_lens"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("seq_lens"), py::arg("group"), py::arg("scale"),
+        py::arg("max_prefix_len"), py::arg("num_splits") = 0);
   m.def("decode_attn_fp8", &decode_attn_fp8,
         "decode_attn over an fp8 (e4m3, per-row scale) KV cache; the "
         "append quantises",

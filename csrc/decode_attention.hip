@@ -13,190 +13,12 @@
 // Split-KV: grid (B*h, splits). With splits > 1 every split writes fp32
 // (acc[D], m, l) to a workspace and a second small launch merges them.
 // No in-launch counters or flags.
-#include "decode_common.h"
+#include "decode_attention_kernel.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 namespace {
-
-constexpr int BLOCK = 256;
-constexpr int NW = BLOCK / WAVE;
-constexpr int UNROLL = 4;   // independent KV rows in flight per lane group
-
-// grid (B*h, splits), 256 threads. Lane group = D/8 lanes, 256/(D/8) groups
-// per block; each group keeps its own running (m, l, acc[8 per lane]) and
-// the groups are merged once at the end (shuffles inside the wave, then
-// NW*(D+2) floats of LDS across waves).
-//
-// ws: fp32 [B*h, splits, D+4] = acc[D], m, l, pad (rows stay 16-byte
-// aligned); only touched when splits > 1
-template <int D>
-__global__ __launch_bounds__(BLOCK) void decode_attn_kernel(
-    const short* __restrict__ qkv,      // [B, 1, h, 3, D] bf16
-    short* __restrict__ k_cache,        // [B, h, Smax, D] bf16
-    short* __restrict__ v_cache,
-    const int* __restrict__ seq_lens,   // [B]
-    short* __restrict__ out,            // [B, 1, h*D] bf16
-    float* __restrict__ ws, int h, int Smax, int chunk, float scale) {
-  constexpr int GL = D / 8;             // lanes per KV row
-  constexpr int NG = BLOCK / GL;        // rows per block step
-  __shared__ float s_acc[NW][D];
-  __shared__ float s_ml[NW][2];
-
-  const int bh = blockIdx.x;
-  const int b = bh / h;
-  const int split = blockIdx.y;
-  const int splits = gridDim.y;
-  const int tid = threadIdx.x;
-  const int g = tid / GL;
-  const int li = tid % GL;
-  const int lane = tid & (WAVE - 1);
-  const int wid = tid / WAVE;
-
-  // a bad length gives wrong numbers, never an out-of-bounds address
-  const int L = min(max(seq_lens[b], 0), Smax - 1);
-  // cached positions [start, end) of this split; the last split runs to L
-  // so an under-estimated max_seq_len cannot drop positions
-  const int start = min(split * chunk, L);
-  const int end = (split == splits - 1) ? L : min((split + 1) * chunk, L);
-
-  const short* qp = qkv + (size_t)bh * 3 * D + li * 8;
-  float q[8];
-  {
-    const short8v qpk = *reinterpret_cast<const short8v*>(qp);
-    unpack8(qpk, q);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) q[i] *= scale;
-  }
-  const short8v knew = *reinterpret_cast<const short8v*>(qp + D);
-  const short8v vnew = *reinterpret_cast<const short8v*>(qp + 2 * D);
-
-  const size_t head_off = (size_t)bh * Smax * D + li * 8;
-  const short* kbase = k_cache + head_off;
-  const short* vbase = v_cache + head_off;
-
-  float m = -INFINITY, l = 0.f;
-  float acc[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-
-  const short8v zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  // block-uniform trip count: every lane stays active for the shuffles
-  for (int base = start; base < end; base += NG * UNROLL) {
-    short8v kk[UNROLL], vv[UNROLL];
-    bool ok[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int p = base + g + u * NG;
-      ok[u] = p < end;
-      // positions >= end are never loaded (they may be uninitialised)
-      kk[u] = ok[u] ? *reinterpret_cast<const short8v*>(kbase + (size_t)p * D)
-                    : zero8;
-      vv[u] = ok[u] ? *reinterpret_cast<const short8v*>(vbase + (size_t)p * D)
-                    : zero8;
-    }
-    float s[UNROLL];
-    float mn = m;
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      float kf[8];
-      unpack8(kk[u], kf);
-      float d = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) d = fmaf(q[i], kf[i], d);
-#pragma unroll
-      for (int off = GL / 2; off > 0; off >>= 1)
-        d += __shfl_xor(d, off, WAVE);
-      s[u] = ok[u] ? d : -INFINITY;
-      mn = fmaxf(mn, s[u]);
-    }
-    // a group past the end of its split has seen nothing yet: mn = -inf
-    const float ms = (mn == -INFINITY) ? 0.f : mn;
-    const float alpha = __expf(m - ms);
-    l *= alpha;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] *= alpha;
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const float pw = ok[u] ? __expf(s[u] - ms) : 0.f;
-      float vf[8];
-      unpack8(vv[u], vf);
-      l += pw;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] = fmaf(pw, vf[i], acc[i]);
-    }
-    m = mn;
-  }
-
-  // new token: appended to the cache and folded in by group 0 of split 0
-  const bool owns_new = (split == 0) && (g == 0);
-  if (owns_new) {
-    *reinterpret_cast<short8v*>(k_cache + head_off + (size_t)L * D) = knew;
-    *reinterpret_cast<short8v*>(v_cache + head_off + (size_t)L * D) = vnew;
-  }
-  {
-    float kf[8], vf[8];
-    unpack8(knew, kf);
-    unpack8(vnew, vf);
-    float d = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d = fmaf(q[i], kf[i], d);
-#pragma unroll
-    for (int off = GL / 2; off > 0; off >>= 1) d += __shfl_xor(d, off, WAVE);
-    const float m_o = owns_new ? d : -INFINITY;
-    const float l_o = owns_new ? 1.f : 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) vf[i] = owns_new ? vf[i] : 0.f;
-    merge_state(m, l, acc, m_o, l_o, vf);
-  }
-
-  // groups inside the wave
-#pragma unroll
-  for (int off = GL; off < WAVE; off <<= 1) {
-    const float m_o = __shfl_xor(m, off, WAVE);
-    const float l_o = __shfl_xor(l, off, WAVE);
-    float acc_o[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc_o[i] = __shfl_xor(acc[i], off, WAVE);
-    merge_state(m, l, acc, m_o, l_o, acc_o);
-  }
-  // waves through LDS
-  if (lane < GL) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s_acc[wid][li * 8 + i] = acc[i];
-    if (lane == 0) { s_ml[wid][0] = m; s_ml[wid][1] = l; }
-  }
-  __syncthreads();
-  if (tid < GL) {
-#pragma unroll
-    for (int w = 1; w < NW; ++w) {
-      float acc_o[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc_o[i] = s_acc[w][li * 8 + i];
-      merge_state(m, l, acc, s_ml[w][0], s_ml[w][1], acc_o);
-    }
-    if (splits == 1) {
-      // l >= 1 term of the new token, so the division is safe
-      const float inv = 1.f / l;
-      short8v o;
-#pragma unroll
-      for (int i = 0; i < 8; i += 2) {
-        const unsigned int u = cvt_pk_bf16(acc[i] * inv, acc[i + 1] * inv);
-        ((unsigned short*)&o)[i] = (unsigned short)u;
-        ((unsigned short*)&o)[i + 1] = (unsigned short)(u >> 16);
-      }
-      *reinterpret_cast<short8v*>(out + (size_t)bh * D + li * 8) = o;
-    } else {
-      float* w = ws + ((size_t)bh * splits + split) * (D + 4);
-      float4v lo = {acc[0], acc[1], acc[2], acc[3]};
-      float4v hi = {acc[4], acc[5], acc[6], acc[7]};
-      *reinterpret_cast<float4v*>(w + li * 8) = lo;
-      *reinterpret_cast<float4v*>(w + li * 8 + 4) = hi;
-      if (tid == 0) { w[D] = m; w[D + 1] = l; }
-    }
-  }
-}
 
 template <int D>
 void launch(torch::Tensor& qkv, torch::Tensor& kc, torch::Tensor& vc,
@@ -215,7 +37,7 @@ void launch(torch::Tensor& qkv, torch::Tensor& kc, torch::Tensor& vc,
                      0, stream, (const short*)qkv.data_ptr(),
                      (short*)kc.data_ptr(), (short*)vc.data_ptr(),
                      lens.data_ptr<int>(), (short*)out.data_ptr(), wsp, (int)h,
-                     (int)Smax, chunk, scale);
+                     (int)Smax, chunk, scale, (const int*)nullptr, 1, 0, 0);
   if (splits > 1)
     hipLaunchKernelGGL(decode_merge_kernel<D>, dim3(B * h), dim3(D), 0, stream,
                        (const float*)wsp, (short*)out.data_ptr(), splits);

@@ -20,6 +20,12 @@ tail by ONE launch per token (csrc/sample_token.hip) that also keeps the
 generation state on the device, so the loop has no host synchronisation
 per token; `capture_decode: true` on top of it records one decode step
 (forward + sampler) as a graph and replays it once per token.
+
+`shared_prompt_cache: true` (sampling with num_return_sequences = G >= 2)
+keeps the G samples of a prompt on ONE copy of the prompt's K/V: the prompt
+is prefilled once per prompt, not once per sample, the static cache stores it
+once, and every decode step reads it once for the whole group
+(csrc/decode_attention_shared.hip).
 """
 
 from __future__ import annotations
@@ -168,6 +174,28 @@ class GPTForGeneration(nn.Module):
             logger.warning("Generation.fused_decode_ln needs model-parallel "
                            "size 1: staying on separate LayerNorms")
             self.fused_decode_ln = False
+        # G samples of a prompt share one stored copy of its K/V
+        self.shared_prompt_cache = bool(cfg.get("shared_prompt_cache", False))
+        if self.shared_prompt_cache:
+            for ok, what in (
+                    (self.static_kv_cache, "static_kv_cache: true (the "
+                     "prompt is stored once in the static cache)"),
+                    (self.fused_sampling, "fused_sampling: true (the shared "
+                     "loop keeps its state on the device)"),
+                    (self.decode_strategy == "sampling",
+                     "decoding_strategy: sampling (greedy samples of one "
+                     "prompt are all the same)"),
+                    (self.num_return_sequences >= 2,
+                     "num_return_sequences >= 2 (one sample shares nothing)"),
+                    (self.kv_cache_dtype == "bf16",
+                     "kv_cache_dtype: bf16 (there is no fp8 prefix)")):
+                if not ok:
+                    raise ValueError(
+                        f"Generation.shared_prompt_cache: true needs {what}")
+            if get_hcg().get_model_parallel_world_size() != 1:
+                logger.warning("Generation.shared_prompt_cache needs "
+                               "model-parallel size 1: staying unshared")
+                self.shared_prompt_cache = False
         # a plain attribute, not a submodule: no state_dict entry, no cast
         self._weight_codes = DecodeWeightCodes(self.decode_weight_dtype) \
             if self.decode_weight_dtype != "bf16" else None
@@ -209,7 +237,16 @@ class GPTForGeneration(nn.Module):
                              max_seq_len=max_seq_len,
                              fused_decode_linear=self.fused_decode_linear,
                              weight_codes=self._weight_codes,
-                             fused_decode_ln=self.fused_decode_ln)
+                             fused_decode_ln=self.fused_decode_ln,
+                             shared_group=self._group,
+                             suffix_len=self.max_length
+                             if self.shared_prompt_cache else None)
+
+    @property
+    def _group(self) -> int:
+        """Rows per prompt of the fused loop's state: G with the shared
+        prompt cache (its input is the P prompts), else 1."""
+        return self.num_return_sequences if self.shared_prompt_cache else 1
 
     # -- fused sampling -----------------------------------------------------
     def _capacity(self, prompt_len: int) -> int:
@@ -266,26 +303,33 @@ class GPTForGeneration(nn.Module):
             u=torch.zeros(B, capacity, dtype=torch.float32, device=device))
 
     def _start(self, st: dict, input_ids: torch.Tensor, kw: dict) -> None:
-        """Reset the state, prefill eagerly and sample the first token."""
-        B, prompt_len = input_ids.shape
+        """Reset the state, prefill eagerly and sample the first token.
+        With the shared prompt cache input_ids holds the P prompts: they are
+        prefilled once each, and the G rows of a prompt draw their first
+        tokens from the same logits, each with its own u."""
+        G = self._group
+        B, prompt_len = input_ids.shape[0] * G, input_ids.shape[1]
         n = prompt_len + self.max_length
         self._refresh_weight_codes()
         cache = st["cache"]
-        cache.lens.zero_()
-        cache.max_len = 0
+        cache.reset()
         st["ids_buf"].fill_(self.pad_token_id)
-        st["ids_buf"][:, :prompt_len] = input_ids
+        # all B rows: the repetition penalty reads the prompt
+        st["ids_buf"][:, :prompt_len] = \
+            input_ids.repeat_interleave(G, dim=0) if G > 1 else input_ids
         st["unfinished"].fill_(True)
         # the only RNG use of a call: seeding reproduces a run, and the draw
         # does not depend on the capacity of the buffers
         st["u"][:, :n] = torch.rand(B, n, device=input_ids.device)
         position_ids = torch.arange(prompt_len, device=input_ids.device) \
-            .unsqueeze(0).expand(B, -1)
+            .unsqueeze(0).expand(input_ids.shape[0], -1)
         hidden, _ = self.gpt(input_ids, position_ids, caches=cache,
                              use_cache=True)
         logits = parallel_matmul(
             hidden[:, -1, :], self.gpt.embeddings.word_embeddings.weight,
             parallel_output=False)
+        if G > 1:
+            logits = logits.repeat_interleave(G, dim=0)
         sample_token(logits, st["ids_buf"], cache.lens, st["unfinished"],
                      st["u"], st["next_tokens"], **kw)
 
@@ -306,7 +350,7 @@ class GPTForGeneration(nn.Module):
         """The loop of sample() with the tail fused into sample_token and no
         host synchronisation per token. return_state also hands back the
         device state (cache, ids_buf, ...) the call ended with."""
-        B, prompt_len = input_ids.shape
+        B, prompt_len = input_ids.shape[0] * self._group, input_ids.shape[1]
         kw = self._sampler_args(prompt_len)
         if self._use_capture(input_ids):
             out = self._sample_captured(input_ids, kw)
@@ -350,8 +394,7 @@ class GPTForGeneration(nn.Module):
         self._refresh_weight_codes()  # never inside the captured region
 
         def reset():
-            cache.lens.zero_()
-            cache.max_len = 0
+            cache.reset()
             st["ids_buf"].fill_(self.pad_token_id)
             st["unfinished"].fill_(True)
             st["next_tokens"].zero_()
@@ -364,22 +407,25 @@ class GPTForGeneration(nn.Module):
         with torch.cuda.stream(side):
             for _ in range(2):
                 self._decode_step(st, kw)
+                # every step from empty: max_dec_len = 1 leaves a row of a
+                # shared-prompt cache room for one token of its own
+                reset()
         torch.cuda.current_stream().wait_stream(side)
-        reset()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             self._decode_step(st, kw)
         reset()
-        st.update(graph=graph, key=(B, tuple(sorted(kw.items()))))
+        st.update(graph=graph,
+                  key=(B, self._group, tuple(sorted(kw.items()))))
         logger.info(f"decode step captured (B={B}, capacity={capacity})")
         return st
 
     def _sample_captured(self, input_ids: torch.Tensor, kw: dict
                          ) -> torch.Tensor:
-        B, prompt_len = input_ids.shape
+        B, prompt_len = input_ids.shape[0] * self._group, input_ids.shape[1]
         capacity = self._capacity(prompt_len)
         # min_length moves with the prompt length and is baked into the graph
-        key = (B, tuple(sorted(kw.items())))
+        key = (B, self._group, tuple(sorted(kw.items())))
         st = self._graph_state
         if st is None or st["key"] != key or \
                 st["cache"].capacity < capacity:
@@ -467,10 +513,13 @@ class GPTForGeneration(nn.Module):
         self.gpt.eval()
         with torch.no_grad():
             if self.decode_strategy == "sampling" and \
-                    self.num_return_sequences > 1:
+                    self.num_return_sequences > 1 and \
+                    not self.shared_prompt_cache:
                 # expand_inputs_for_generation (single_model.py:1408-1412):
                 # each prompt row is repeated n times, so the output is
-                # [B*n, max_dec_len] grouped by prompt
+                # [B*n, max_dec_len] grouped by prompt. The shared prompt
+                # cache expands inside the fused loop instead (_start):
+                # same output shape and grouping
                 input_ids = input_ids.repeat_interleave(
                     self.num_return_sequences, dim=0)
             out = self.sample(input_ids)

@@ -23,7 +23,8 @@ import torch.nn.functional as F
 from torch.utils.checkpoint import checkpoint
 
 from paddlefleetx_amd.ops import (FusedLayerNorm, bias_gelu,
-                                  decode_attention, decode_linear,
+                                  decode_attention, decode_attention_shared,
+                                  decode_linear,
                                   flash_attention,
                                   flash_attention_packed,
                                   fused_softmax_causal, kv_cache_store_fp8)
@@ -48,19 +49,28 @@ KVCache = Tuple[torch.Tensor, torch.Tensor]  # ([B,H,S,D] k, [B,H,S,D] v)
 class StaticKVSlot:
     """One layer's view of a StaticKVCache: its k/v buffers (plus the
     per-row scales of an fp8 cache, else None) and the shared lengths.
+    A shared-prompt cache adds the layer's prefix buffers (else None).
     Layers read `lens`/`max_len`, never write them."""
 
-    __slots__ = ("owner", "k", "v", "k_scale", "v_scale")
+    __slots__ = ("owner", "k", "v", "k_scale", "v_scale", "k_prefix",
+                 "v_prefix")
 
     def __init__(self, owner: "StaticKVCache", k: torch.Tensor,
                  v: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
-                 v_scale: Optional[torch.Tensor] = None):
+                 v_scale: Optional[torch.Tensor] = None,
+                 k_prefix: Optional[torch.Tensor] = None,
+                 v_prefix: Optional[torch.Tensor] = None):
         self.owner, self.k, self.v = owner, k, v
         self.k_scale, self.v_scale = k_scale, v_scale
+        self.k_prefix, self.v_prefix = k_prefix, v_prefix
 
     @property
     def fp8(self) -> bool:
         return self.k_scale is not None
+
+    @property
+    def shared(self) -> bool:
+        return self.k_prefix is not None
 
 
 class DecodeWeightCodes:
@@ -171,6 +181,17 @@ class StaticKVCache:
     weight_codes (Generation.decode_weight_dtype: fp8): a DecodeWeightCodes
     those layers take fp8 codes and scales from instead of the bf16
     weights; None (the default) streams the parameters themselves.
+
+    shared_group = G >= 2 (Generation.shared_prompt_cache, bf16 only): the
+    batch is P = batch_size / G prompts with G samples each, rows grouped by
+    prompt. Each prompt's K/V are stored once, in per-layer k_prefix/v_prefix
+    [P, h, max_len - suffix_len, D] with a device int32 prefix_lens[P]; k/v
+    shrink to [B, h, suffix_len, D] and hold only the tokens a row generated
+    itself. P*Lp + B*suffix_len rows instead of B*(Lp + suffix_len). lens[B]
+    and max_len stay TOTAL lengths. A forward of P rows is the prefill (it
+    fills the prefix buffers, sets prefix_lens, and sets lens of all B rows
+    to the prompt length); a forward of B rows of one token is a decode step
+    (ops.decode_attention_shared).
     """
 
     def __init__(self, num_layers: int, batch_size: int, num_heads: int,
@@ -180,7 +201,8 @@ class StaticKVCache:
                  max_seq_len: Optional[int] = None,
                  fused_decode_linear: bool = False,
                  weight_codes: Optional[DecodeWeightCodes] = None,
-                 fused_decode_ln: bool = False):
+                 fused_decode_ln: bool = False, shared_group: int = 1,
+                 suffix_len: Optional[int] = None):
         assert kv_dtype in (None, "bf16", "fp8"), \
             f"StaticKVCache: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}"
         self.kv_dtype = "fp8" if kv_dtype == "fp8" else "bf16"
@@ -195,7 +217,30 @@ class StaticKVCache:
         self.fused_decode_ln = bool(fused_decode_ln)
         assert not self.fused_decode_ln or self.fused_decode_linear, \
             "StaticKVCache: fused_decode_ln needs fused_decode_linear"
+        self.batch_size = int(batch_size)
+        self.group = int(shared_group)
         shape = (batch_size, num_heads, self.capacity, head_dim)
+        self.k_prefix = self.v_prefix = self.prefix_lens = None
+        self.prefix_max_len = 0  # host mirror of max(prefix_lens)
+        if self.group > 1:
+            assert self.kv_dtype == "bf16", \
+                "StaticKVCache: a shared-prompt cache is bf16 only"
+            assert batch_size % self.group == 0, \
+                f"StaticKVCache: batch {batch_size} is no multiple of " \
+                f"shared_group {self.group}"
+            assert suffix_len is not None and \
+                1 <= int(suffix_len) < self.capacity, \
+                f"StaticKVCache: suffix_len {suffix_len} not in " \
+                f"[1, {self.capacity})"
+            pshape = (batch_size // self.group, num_heads,
+                      self.capacity - int(suffix_len), head_dim)
+            self.k_prefix = [torch.empty(pshape, dtype=dtype, device=device)
+                             for _ in range(num_layers)]
+            self.v_prefix = [torch.empty(pshape, dtype=dtype, device=device)
+                             for _ in range(num_layers)]
+            self.prefix_lens = torch.zeros(pshape[0], dtype=torch.int32,
+                                           device=device)
+            shape = (batch_size, num_heads, int(suffix_len), head_dim)
         if self.kv_dtype == "fp8":
             dtype = torch.float8_e4m3fn
         self.k = [torch.empty(shape, dtype=dtype, device=device)
@@ -215,9 +260,28 @@ class StaticKVCache:
 
     @property
     def nbytes(self) -> int:
-        """Bytes of the K/V buffers (and scales) over all layers."""
-        bufs = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        """Bytes of the K/V buffers (and scales, and the prompt prefixes of
+        a shared-prompt cache) over all layers."""
+        bufs = self.k + self.v + (self.k_scale or []) + (self.v_scale or []) \
+            + (self.k_prefix or []) + (self.v_prefix or [])
         return sum(t.numel() * t.element_size() for t in bufs)
+
+    @property
+    def num_prompts(self) -> int:
+        return self.batch_size // self.group
+
+    def is_prefill(self, rows: int) -> bool:
+        """Shared-prompt cache only: a forward of P (not B) rows fills the
+        prefix buffers."""
+        return self.group > 1 and rows == self.num_prompts
+
+    def reset(self) -> None:
+        """Empty the cache (the buffers keep their stale contents)."""
+        self.lens.zero_()
+        self.max_len = 0
+        if self.group > 1:
+            self.prefix_lens.zero_()
+            self.prefix_max_len = 0
 
     def __len__(self) -> int:
         return len(self.k)
@@ -226,11 +290,30 @@ class StaticKVCache:
         if self.kv_dtype == "fp8":
             return StaticKVSlot(self, self.k[i], self.v[i], self.k_scale[i],
                                 self.v_scale[i])
+        if self.group > 1:
+            return StaticKVSlot(self, self.k[i], self.v[i],
+                                k_prefix=self.k_prefix[i],
+                                v_prefix=self.v_prefix[i])
         return StaticKVSlot(self, self.k[i], self.v[i])
 
-    def advance(self, n: int) -> None:
+    def advance(self, n: int, rows: Optional[int] = None) -> None:
+        """Move every length by n tokens. rows: batch rows of the forward
+        that appended them (a shared-prompt cache tells its prefill by it)."""
         assert self.max_len + n <= self.capacity, \
             f"StaticKVCache overflow: {self.max_len}+{n} > {self.capacity}"
+        if self.group > 1:
+            if rows is not None and self.is_prefill(rows):
+                assert self.max_len == 0 and \
+                    n <= self.k_prefix[0].shape[2], \
+                    "StaticKVCache: shared prefill needs an empty cache and " \
+                    f"a prompt of <= {self.k_prefix[0].shape[2]} tokens"
+                self.prefix_lens.fill_(n)
+                self.prefix_max_len = n
+            else:
+                own = self.max_len - self.prefix_max_len
+                assert own + n <= self.k[0].shape[2], \
+                    f"StaticKVCache overflow: {own}+{n} own tokens > " \
+                    f"{self.k[0].shape[2]}"
         self.lens += n
         self.max_len += n
 
@@ -388,6 +471,16 @@ class MultiHeadAttention(nn.Module):
         n_cached = slot.owner.max_len
         assert n_cached + S <= slot.owner.capacity, \
             f"StaticKVCache overflow: {n_cached}+{S} > {slot.owner.capacity}"
+        if slot.shared:
+            own = slot.owner
+            assert B == own.batch_size, \
+                f"shared-prompt decode needs all {own.batch_size} rows"
+            fixed = own.max_seq_len is not None
+            return decode_attention_shared(
+                packed, slot.k_prefix, slot.v_prefix, own.prefix_lens,
+                slot.k, slot.v, own.lens, own.group, scale=self.scale,
+                max_prefix_len=slot.k_prefix.shape[2] if fixed
+                else max(own.prefix_max_len, 1))
         return decode_attention(packed, slot.k, slot.v, slot.owner.lens,
                                 scale=self.scale,
                                 max_seq_len=slot.owner.max_seq_len
@@ -408,11 +501,22 @@ class MultiHeadAttention(nn.Module):
         n_cached = slot.owner.max_len
         assert n_cached + S <= slot.owner.capacity, \
             f"StaticKVCache overflow: {n_cached}+{S} > {slot.owner.capacity}"
-        if S == 1:
+        prefill = slot.shared and slot.owner.is_prefill(B)
+        if S == 1 and not prefill:
             return self.out_proj(self._decode_core(qkv, slot)), slot
         assert n_cached == 0, \
             "StaticKVCache prefill (S > 1) needs an empty cache"
-        if slot.fp8:
+        if slot.shared:
+            # P prompt rows, stored once; the B rows' own caches stay empty
+            assert prefill and S <= slot.k_prefix.shape[2], \
+                "shared-prompt prefill takes the P prompt rows, at most " \
+                f"{slot.k_prefix.shape[2]} tokens"
+            slot.k_prefix[:, :, :S].copy_(packed[:, :, :, 1].transpose(1, 2))
+            slot.v_prefix[:, :, :S].copy_(packed[:, :, :, 2].transpose(1, 2))
+            if S == 1:  # softmax over one token: the output is its V
+                o = packed[:, :, :, 2].reshape(B, S, -1)
+                return self.out_proj(o), slot
+        elif slot.fp8:
             # one quantising launch; attention below still runs on bf16 qkv
             kv_cache_store_fp8(packed, slot.k, slot.v, slot.k_scale,
                                slot.v_scale)
@@ -562,6 +666,7 @@ class TransformerDecoderLayer(nn.Module):
         if (isinstance(cache, StaticKVSlot)
                 and cache.owner.fused_decode_linear
                 and x.shape[1] == 1 and not self.training
+                and not cache.owner.is_prefill(x.shape[0])
                 and isinstance(self.ffn, FFN) and not self.sequence_parallel):
             z = self._forward_decode_fused(x, cache)
             return (z, cache) if use_cache else z
@@ -696,7 +801,7 @@ class GPTModel(nn.Module):
                 x = layer(x, cache=cache_i)
         if isinstance(caches, StaticKVCache):
             # every layer appended at the same lens; move them once
-            caches.advance(input_ids.shape[1])
+            caches.advance(input_ids.shape[1], rows=input_ids.shape[0])
             new_caches = caches
         if apply_final_ln:
             x = self.final_ln(x)

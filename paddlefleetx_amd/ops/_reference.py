@@ -204,6 +204,51 @@ def decode_attention(qkv: torch.Tensor, k_cache: torch.Tensor,
     return o.reshape(B, 1, h * D).to(qkv.dtype)
 
 
+def decode_attention_shared(qkv: torch.Tensor, k_prefix: torch.Tensor,
+                            v_prefix: torch.Tensor, prefix_lens: torch.Tensor,
+                            k_cache: torch.Tensor, v_cache: torch.Tensor,
+                            seq_lens: torch.Tensor, group: int,
+                            scale: Optional[float] = None) -> torch.Tensor:
+    """decode_attention for B = P * group rows grouped by prompt, fp32 math.
+
+    k_prefix/v_prefix [P, h, Lcap, D] hold each prompt's K/V once
+    (prefix_lens [P] valid positions); k_cache/v_cache [B, h, Scap, D] hold
+    every row's own tokens. seq_lens [B] is the TOTAL length per row: the
+    new token is appended IN PLACE at position seq_lens[b] -
+    prefix_lens[b // group] of the row's cache. The softmax runs over
+    prefix, own tokens and the new token; nothing past either length is
+    read. Returns [B, 1, h*D] in qkv.dtype.
+    """
+    B, _, h, _, D = qkv.shape
+    P, _, Lcap, _ = k_prefix.shape
+    Scap = k_cache.shape[2]
+    assert group >= 1 and P * group == B, \
+        "decode_attention_shared: P * group must equal B"
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    q, k_new, v_new = qkv[:, 0, :, 0], qkv[:, 0, :, 1], qkv[:, 0, :, 2]
+    plens = prefix_lens.long().clamp(0, Lcap).repeat_interleave(group)
+    slens = (seq_lens.long() - plens).clamp(0, Scap - 1)
+    rows = torch.arange(B, device=qkv.device)
+    k_cache[rows, :, slens] = k_new.to(k_cache.dtype)
+    v_cache[rows, :, slens] = v_new.to(v_cache.dtype)
+    valid = torch.cat(
+        (torch.arange(Lcap, device=qkv.device)[None, :] < plens[:, None],
+         torch.arange(Scap, device=qkv.device)[None, :] <= slens[:, None]),
+        dim=1)[:, None, :]  # [B, 1, Lcap + Scap]
+    kf = torch.cat((k_prefix.float().repeat_interleave(group, dim=0),
+                    k_cache.float()), dim=2)
+    vf = torch.cat((v_prefix.float().repeat_interleave(group, dim=0),
+                    v_cache.float()), dim=2)
+    # select, never multiply: the tails may hold NaN/Inf
+    kf = torch.where(valid[..., None], kf, 0.0)
+    vf = torch.where(valid[..., None], vf, 0.0)
+    s = torch.einsum("bhd,bhsd->bhs", q.float(), kf) * scale
+    s = s.masked_fill(~valid, float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    o = torch.einsum("bhs,bhsd->bhd", p, vf)
+    return o.reshape(B, 1, h * D).to(qkv.dtype)
+
+
 FP8_MAX = 448.0  # largest finite float8_e4m3fn
 
 

@@ -614,6 +614,50 @@ def decode_attention(qkv, k_cache, v_cache, seq_lens,
     return ref.decode_attention(qkv, k_cache, v_cache, seq_lens, scale)
 
 
+def decode_attention_shared(qkv, k_prefix, v_prefix, prefix_lens,
+                            k_cache, v_cache, seq_lens, group: int,
+                            scale: Optional[float] = None,
+                            max_prefix_len: Optional[int] = None,
+                            num_splits: Optional[int] = None):
+    """decode_attention for G = group samples of each prompt, the prompt's
+    K/V stored and read ONCE per prompt (inference only).
+
+    qkv [B, 1, h, 3, D], B = P*G, rows grouped by prompt (row b belongs to
+    prompt b // G). k_prefix/v_prefix [P, h, Lcap, D] hold the prompts'
+    K/V, prefix_lens (int32 [P], on the device) their lengths.
+    k_cache/v_cache [B, h, Scap, D] hold each row's own generated tokens;
+    seq_lens (int32 [B]) is the TOTAL length per row, prefix included, so
+    the new K/V are appended IN PLACE at position seq_lens[b] -
+    prefix_lens[b // G] of the row's cache. Neither length tensor is
+    written. Returns [B, 1, h*D].
+
+    max_prefix_len: host upper bound on max(prefix_lens) (sizes the prefix
+    chunks; default Lcap). num_splits: prefix chunks, None/0 = automatic,
+    1..31 forced.
+
+    Dispatch as decode_attention: bf16 CUDA tensors with D in {64, 128}
+    run the HIP kernels (csrc/decode_attention_shared.hip: an MFMA pass
+    over the shared prefix, the decode_attention walk over the row's own
+    tokens, one merge; an error if the extension is missing); everything
+    else runs the fp32 reference twin with the same in-place semantics.
+    """
+    assert not (torch.is_grad_enabled() and (
+        qkv.requires_grad or k_cache.requires_grad or v_cache.requires_grad
+        or k_prefix.requires_grad or v_prefix.requires_grad)), \
+        "decode_attention_shared is inference-only (no autograd)"
+    D = qkv.shape[-1]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if use_hip(qkv) and qkv.dtype == torch.bfloat16 and D in (64, 128):
+        mpl = int(max_prefix_len) if max_prefix_len is not None \
+            else k_prefix.shape[2]
+        return hip_ext().decode_attn_shared(
+            qkv, k_prefix, v_prefix, prefix_lens, k_cache, v_cache, seq_lens,
+            int(group), float(scale), mpl, int(num_splits or 0))
+    return ref.decode_attention_shared(qkv, k_prefix, v_prefix, prefix_lens,
+                                       k_cache, v_cache, seq_lens, int(group),
+                                       scale)
+
+
 def kv_cache_store_fp8(qkv, k_cache, v_cache, k_scale, v_scale) -> None:
     """Prefill store into an fp8 KV cache (inference only).
 

@@ -28,7 +28,8 @@ hip_sources = [
     os.path.join(CSRC, s)
     for s in ("bindings.cpp", "layernorm.hip", "elementwise.hip",
               "softmax.hip", "attention.hip", "decode_attention.hip",
-              "decode_attention_fp8.hip", "decode_linear.hip",
+              "decode_attention_fp8.hip", "decode_attention_shared.hip",
+              "decode_linear.hip",
               "decode_linear_fp8.hip", "decode_linear_mxfp4.hip",
               "decode_linear_wide.hip", "decode_linear_wide_mxfp4.hip",
               "linear_codes.hip", "topp.hip",
