@@ -18,6 +18,10 @@ decode_attention_shared (csrc/decode_attention_shared.hip) on P = 16/G prompts
 stored once, 8 own tokens per row; effective bytes are what each variant has
 to read. --splits lists forced prefix chunk counts to time (0 = the rule).
 
+With --shared G --kv-dtype fp8 the two variants are the shared-prompt op with
+a bf16 prefix and with an fp8 prefix (csrc/decode_attention_shared_fp8.hip) on
+the same data, two rounds, the worst pairing reported.
+
 Device-event timing, warm-up, the two variants alternate inside one process
 and the median over the repetitions is reported. Bytes are the K/V the
 algorithm has to read, 2*B*h*(L+1)*D*2, so GB/s is an ALGORITHMIC rate: the
@@ -86,6 +90,8 @@ def main():
     hip_ext()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if args.shared and args.kv_dtype == "fp8":
+        return sweep_shared_fp8(args, dev)
     if args.shared:
         return sweep_shared(args, dev)
     if args.kv_dtype == "fp8":
@@ -265,6 +271,75 @@ def sweep_shared(args, dev):
                   f"{min(t_e):.2f}/{max(t_e):.2f}, shared {min(t_s):.2f}/"
                   f"{max(t_s):.2f}; max|diff| {err:.4f})")
         del sets_e, sets_s
+
+
+def sweep_shared_fp8(args, dev):
+    """The shared-prompt op with a bf16 prefix vs an fp8 prefix
+    (csrc/decode_attention_shared_fp8.hip), alternating, two rounds; the
+    ratio reported is the worst pairing (fastest bf16 median over slowest
+    fp8 median). Each op's bytes are its own: the prefix 2*P*h*L*D*2 or
+    2*P*h*L*(D+4), plus the rows' bf16 own tokens."""
+    from paddlefleetx_amd.ops import _reference as ref
+    from paddlefleetx_amd.ops import decode_attention_shared
+    G, B, h, D, own = args.shared, 16, 16, 128, 8
+    assert B % G == 0, "--shared G must divide 16"
+    P = B // G
+    splits = [int(x) for x in args.splits.split(",")]
+    print(f"# shared-prompt decode attention, bf16 vs fp8 prefix (G={G}, "
+          f"P={P}), on {torch.cuda.get_device_name(0)}; iters={args.iters} "
+          f"reps={args.reps} rounds=2; h={h} D={D}, {own} own tokens per row")
+    print(f"{'G':>3} {'L':>5} {'chunks':>6} | {'MiB':>7} {'bf16 us':>15} "
+          f"{'TB/s':>5} | {'MiB':>7} {'fp8 us':>15} {'TB/s':>5} | "
+          f"bf16/fp8 (worst pairing)")
+    scale = 1.0 / math.sqrt(D)
+    for L in (128, 2048):
+        tail = 2 * h * B * (own + 1) * D * 2
+        nb, nf = 2 * P * h * L * D * 2 + tail, 2 * P * h * L * (D + 4) + tail
+        sets_b, sets_f = [], []
+        for i in range(num_sets(nf, args.max_sets)):
+            qkv = torch.randn(B, 1, h, 3, D, device=dev).to(torch.bfloat16)
+            kp = torch.randn(P, h, L, D, device=dev).to(torch.bfloat16)
+            vp = torch.randn(P, h, L, D, device=dev).to(torch.bfloat16)
+            kc = torch.randn(B, h, own + 1, D, device=dev).to(torch.bfloat16)
+            vc = torch.randn(B, h, own + 1, D, device=dev).to(torch.bfloat16)
+            sets_f.append((qkv, *ref.quantize_kv_rows(kp),
+                           *ref.quantize_kv_rows(vp), kc, vc))
+            if i < num_sets(nb, args.max_sets):
+                sets_b.append((qkv, kp, vp, kc, vc))
+        lens = torch.full((B,), L + own, dtype=torch.int32, device=dev)
+        plens = torch.full((P,), L, dtype=torch.int32, device=dev)
+        for ns_ in splits:
+            def bf16(s):
+                return decode_attention_shared(
+                    s[0], s[1], s[2], plens, s[3], s[4], lens, G, scale=scale,
+                    max_prefix_len=L, num_splits=ns_)
+
+            def fp8(s):
+                return decode_attention_shared(
+                    s[0], s[1], s[3], plens, s[5], s[6], lens, G, scale=scale,
+                    max_prefix_len=L, num_splits=ns_, k_prefix_scale=s[2],
+                    v_prefix_scale=s[4])
+
+            ub, uf = [], []
+            with torch.no_grad():
+                err = (bf16(sets_b[0]).float()
+                       - fp8(sets_f[0]).float()).abs().max().item()
+                assert err < 1e-1, f"variants disagree: {err}"
+                for _ in range(2):
+                    time_block(bf16, sets_b, args.iters)  # warm-up
+                    time_block(fp8, sets_f, args.iters)
+                    t_b, t_f = [], []
+                    for _ in range(args.reps):
+                        t_b.append(time_block(bf16, sets_b, args.iters))
+                        t_f.append(time_block(fp8, sets_f, args.iters))
+                    ub.append(statistics.median(t_b))
+                    uf.append(statistics.median(t_f))
+            print(f"{G:3d} {L:5d} {ns_:6d} | {len(sets_b) * nb / 2**20:7.1f} "
+                  f"{ub[0]:7.2f}/{ub[1]:7.2f} {nb / max(ub) / 1e6:5.2f} | "
+                  f"{len(sets_f) * nf / 2**20:7.1f} {uf[0]:7.2f}/{uf[1]:7.2f} "
+                  f"{nf / max(uf) / 1e6:5.2f} | {min(ub) / max(uf):5.2f}x  "
+                  f"(max|diff| {err:.4f})")
+        del sets_b, sets_f
 
 
 if __name__ == "__main__":

@@ -85,6 +85,9 @@ def main():
                         "alternating in one process (needs --static-cache "
                         "--fused-sampling and G >= 2); also prints the time "
                         "of prefill + first token and the cache bytes")
+    p.add_argument("--shared-prompt-fp8", action="store_true",
+                   help="as --shared-prompt, but both sides share the prompt: "
+                        "Generation.shared_prompt_dtype bf16 against fp8")
     p.add_argument("--finish-check-interval", type=int, default=None,
                    help="Generation.finish_check_interval (fused sampling)")
     p.add_argument("--fixed-capacity", action="store_true",
@@ -103,6 +106,10 @@ def main():
     if args.weight_dtype != "bf16" and not args.fused_linear:
         p.error(f"--weight-dtype {args.weight_dtype} needs --fused-linear")
 
+    if args.shared_prompt_fp8:
+        if args.shared_prompt:
+            p.error("--shared-prompt-fp8 replaces --shared-prompt")
+        args.shared_prompt = True
     if args.shared_prompt and (args.alternate_wide_linear
                                or args.alternate_linear_codes):
         p.error("--shared-prompt is an alternation of its own")
@@ -134,6 +141,9 @@ def main():
     if args.shared_prompt:
         modes = [("unshared ",) + modes[0][1:3] + (False,),
                  ("shared   ",) + modes[0][1:3] + (True,)]
+    if args.shared_prompt_fp8:  # the last field: False, True or "fp8"
+        modes = [("shared bf16 ",) + modes[0][1:3] + (True,),
+                 ("shared fp8  ",) + modes[0][1:3] + ("fp8",)]
     torch.manual_seed(0)
     with torch.device(dev):
         gpt = GPTModel(vocab_size=vocab, max_position_embeddings=max_len,
@@ -141,7 +151,8 @@ def main():
         models = [GPTForGeneration(gpt, {
             "max_dec_len": gen_len,
             "num_return_sequences": args.num_return_sequences,
-            "shared_prompt_cache": m[3],
+            "shared_prompt_cache": bool(m[3]),
+            "shared_prompt_dtype": "fp8" if m[3] == "fp8" else "bf16",
             "decoding_strategy": "sampling",
             "top_p": args.top_p,
             "use_topp_sampling": True,

@@ -81,6 +81,13 @@ torch::Tensor decode_attn_shared(torch::Tensor qkv, torch::Tensor k_prefix,
                                  torch::Tensor seq_lens, long group,
                                  double scale, long max_prefix_len,
                                  long num_splits);
+// decode_attention_shared_fp8.hip
+torch::Tensor decode_attn_shared_fp8(
+    torch::Tensor qkv, torch::Tensor k_prefix, torch::Tensor v_prefix,
+    torch::Tensor k_prefix_scale, torch::Tensor v_prefix_scale,
+    torch::Tensor prefix_lens, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor seq_lens, long group, double scale, long max_prefix_len,
+    long num_splits);
 // decode_attention_fp8.hip
 torch::Tensor decode_attn_fp8(torch::Tensor qkv, torch::Tensor k_cache,
                               torch::Tensor v_cache, torch::Tensor k_scale,
@@ -212,6 +219,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "position seq_lens[b] - prefix_lens[b / group] of the row's cache "
         "(num_splits: prefix chunks, 0 automatic)",
         py::arg("qkv"), py::arg("k_prefix"), py::arg("v_prefix"),
+        py::arg("prefix_lens"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("seq_lens"), py::arg("group"), py::arg("scale"),
+        py::arg("max_prefix_len"), py::arg("num_splits") = 0);
+  m.def("decode_attn_shared_fp8", &decode_attn_shared_fp8,
+        "decode_attn_shared with the prompt prefix stored as float8_e4m3fn "
+        "codes [P, h, Lcap, D] and one fp32 scale per stored row [P, h, "
+        "Lcap] (the layout kv_store_fp8 writes); k_cache/v_cache stay bf16",
+        py::arg("qkv"), py::arg("k_prefix"), py::arg("v_prefix"),
+        py::arg("k_prefix_scale"), py::arg("v_prefix_scale"),
         py::arg("prefix_lens"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("seq_lens"), py::arg("group"), py::arg("scale"),
         py::arg("max_prefix_len"), py::arg("num_splits") = 0);

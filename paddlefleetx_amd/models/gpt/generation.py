@@ -25,7 +25,9 @@ per token; `capture_decode: true` on top of it records one decode step
 keeps the G samples of a prompt on ONE copy of the prompt's K/V: the prompt
 is prefilled once per prompt, not once per sample, the static cache stores it
 once, and every decode step reads it once for the whole group
-(csrc/decode_attention_shared.hip).
+(csrc/decode_attention_shared.hip). `shared_prompt_dtype: fp8` stores that
+copy as e4m3 codes with a per-row scale (csrc/decode_attention_shared_fp8.hip);
+the tokens a sample generates stay bf16.
 """
 
 from __future__ import annotations
@@ -188,10 +190,25 @@ class GPTForGeneration(nn.Module):
                     (self.num_return_sequences >= 2,
                      "num_return_sequences >= 2 (one sample shares nothing)"),
                     (self.kv_cache_dtype == "bf16",
-                     "kv_cache_dtype: bf16 (there is no fp8 prefix)")):
+                     "kv_cache_dtype: bf16 (the rows' own cache is bf16; "
+                     "shared_prompt_dtype: fp8 stores the prompt as fp8)")):
                 if not ok:
                     raise ValueError(
                         f"Generation.shared_prompt_cache: true needs {what}")
+        # storage of the shared prompt: "bf16" or "fp8" (e4m3 codes + one
+        # fp32 scale per prompt row; the rows' own tokens stay bf16)
+        self.shared_prompt_dtype = str(cfg.get("shared_prompt_dtype")
+                                       or "bf16")
+        if self.shared_prompt_dtype not in ("bf16", "fp8"):
+            raise ValueError(
+                "Generation.shared_prompt_dtype must be 'bf16' or 'fp8', got "
+                f"{self.shared_prompt_dtype!r}")
+        if self.shared_prompt_dtype == "fp8" and \
+                not cfg.get("shared_prompt_cache", False):
+            raise ValueError(
+                "Generation.shared_prompt_dtype: fp8 needs "
+                "shared_prompt_cache: true (it is the stored prompt's dtype)")
+        if self.shared_prompt_cache:
             if get_hcg().get_model_parallel_world_size() != 1:
                 logger.warning("Generation.shared_prompt_cache needs "
                                "model-parallel size 1: staying unshared")
@@ -240,6 +257,8 @@ class GPTForGeneration(nn.Module):
                              fused_decode_ln=self.fused_decode_ln,
                              shared_group=self._group,
                              suffix_len=self.max_length
+                             if self.shared_prompt_cache else None,
+                             shared_prefix_dtype=self.shared_prompt_dtype
                              if self.shared_prompt_cache else None)
 
     @property

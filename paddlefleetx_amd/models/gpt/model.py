@@ -49,20 +49,25 @@ KVCache = Tuple[torch.Tensor, torch.Tensor]  # ([B,H,S,D] k, [B,H,S,D] v)
 class StaticKVSlot:
     """One layer's view of a StaticKVCache: its k/v buffers (plus the
     per-row scales of an fp8 cache, else None) and the shared lengths.
-    A shared-prompt cache adds the layer's prefix buffers (else None).
+    A shared-prompt cache adds the layer's prefix buffers (else None), an
+    fp8 prefix its per-row scales too.
     Layers read `lens`/`max_len`, never write them."""
 
     __slots__ = ("owner", "k", "v", "k_scale", "v_scale", "k_prefix",
-                 "v_prefix")
+                 "v_prefix", "k_prefix_scale", "v_prefix_scale")
 
     def __init__(self, owner: "StaticKVCache", k: torch.Tensor,
                  v: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
                  v_scale: Optional[torch.Tensor] = None,
                  k_prefix: Optional[torch.Tensor] = None,
-                 v_prefix: Optional[torch.Tensor] = None):
+                 v_prefix: Optional[torch.Tensor] = None,
+                 k_prefix_scale: Optional[torch.Tensor] = None,
+                 v_prefix_scale: Optional[torch.Tensor] = None):
         self.owner, self.k, self.v = owner, k, v
         self.k_scale, self.v_scale = k_scale, v_scale
         self.k_prefix, self.v_prefix = k_prefix, v_prefix
+        self.k_prefix_scale = k_prefix_scale
+        self.v_prefix_scale = v_prefix_scale
 
     @property
     def fp8(self) -> bool:
@@ -182,7 +187,7 @@ class StaticKVCache:
     those layers take fp8 codes and scales from instead of the bf16
     weights; None (the default) streams the parameters themselves.
 
-    shared_group = G >= 2 (Generation.shared_prompt_cache, bf16 only): the
+    shared_group = G >= 2 (Generation.shared_prompt_cache, kv_dtype bf16): the
     batch is P = batch_size / G prompts with G samples each, rows grouped by
     prompt. Each prompt's K/V are stored once, in per-layer k_prefix/v_prefix
     [P, h, max_len - suffix_len, D] with a device int32 prefix_lens[P]; k/v
@@ -192,6 +197,12 @@ class StaticKVCache:
     fills the prefix buffers, sets prefix_lens, and sets lens of all B rows
     to the prompt length); a forward of B rows of one token is a decode step
     (ops.decode_attention_shared).
+
+    shared_prefix_dtype "fp8" (Generation.shared_prompt_dtype; needs
+    shared_group >= 2 and a bf16 kv_dtype): k_prefix/v_prefix hold
+    float8_e4m3fn codes and per-layer k_prefix_scale/v_prefix_scale
+    [P, h, max_len - suffix_len] fp32 one scale per stored prompt row, D + 4
+    bytes per row instead of 2*D. k/v, the rows' own tokens, stay bf16.
     """
 
     def __init__(self, num_layers: int, batch_size: int, num_heads: int,
@@ -202,7 +213,8 @@ class StaticKVCache:
                  fused_decode_linear: bool = False,
                  weight_codes: Optional[DecodeWeightCodes] = None,
                  fused_decode_ln: bool = False, shared_group: int = 1,
-                 suffix_len: Optional[int] = None):
+                 suffix_len: Optional[int] = None,
+                 shared_prefix_dtype: Optional[str] = None):
         assert kv_dtype in (None, "bf16", "fp8"), \
             f"StaticKVCache: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}"
         self.kv_dtype = "fp8" if kv_dtype == "fp8" else "bf16"
@@ -221,6 +233,16 @@ class StaticKVCache:
         self.group = int(shared_group)
         shape = (batch_size, num_heads, self.capacity, head_dim)
         self.k_prefix = self.v_prefix = self.prefix_lens = None
+        self.k_prefix_scale = self.v_prefix_scale = None
+        assert shared_prefix_dtype in (None, "bf16", "fp8"), \
+            "StaticKVCache: shared_prefix_dtype must be 'bf16' or 'fp8', " \
+            f"got {shared_prefix_dtype!r}"
+        self.shared_prefix_dtype = \
+            "fp8" if shared_prefix_dtype == "fp8" else "bf16"
+        assert self.shared_prefix_dtype == "bf16" or (
+            self.group > 1 and self.kv_dtype == "bf16"), \
+            "StaticKVCache: shared_prefix_dtype 'fp8' needs shared_group " \
+            ">= 2 and kv_dtype 'bf16' (only the prefix is fp8)"
         self.prefix_max_len = 0  # host mirror of max(prefix_lens)
         if self.group > 1:
             assert self.kv_dtype == "bf16", \
@@ -234,9 +256,18 @@ class StaticKVCache:
                 f"[1, {self.capacity})"
             pshape = (batch_size // self.group, num_heads,
                       self.capacity - int(suffix_len), head_dim)
-            self.k_prefix = [torch.empty(pshape, dtype=dtype, device=device)
+            pdtype = dtype
+            if self.shared_prefix_dtype == "fp8":
+                pdtype = torch.float8_e4m3fn
+                self.k_prefix_scale = [
+                    torch.empty(pshape[:3], dtype=torch.float32,
+                                device=device) for _ in range(num_layers)]
+                self.v_prefix_scale = [
+                    torch.empty(pshape[:3], dtype=torch.float32,
+                                device=device) for _ in range(num_layers)]
+            self.k_prefix = [torch.empty(pshape, dtype=pdtype, device=device)
                              for _ in range(num_layers)]
-            self.v_prefix = [torch.empty(pshape, dtype=dtype, device=device)
+            self.v_prefix = [torch.empty(pshape, dtype=pdtype, device=device)
                              for _ in range(num_layers)]
             self.prefix_lens = torch.zeros(pshape[0], dtype=torch.int32,
                                            device=device)
@@ -263,7 +294,8 @@ class StaticKVCache:
         """Bytes of the K/V buffers (and scales, and the prompt prefixes of
         a shared-prompt cache) over all layers."""
         bufs = self.k + self.v + (self.k_scale or []) + (self.v_scale or []) \
-            + (self.k_prefix or []) + (self.v_prefix or [])
+            + (self.k_prefix or []) + (self.v_prefix or []) \
+            + (self.k_prefix_scale or []) + (self.v_prefix_scale or [])
         return sum(t.numel() * t.element_size() for t in bufs)
 
     @property
@@ -291,9 +323,12 @@ class StaticKVCache:
             return StaticKVSlot(self, self.k[i], self.v[i], self.k_scale[i],
                                 self.v_scale[i])
         if self.group > 1:
-            return StaticKVSlot(self, self.k[i], self.v[i],
-                                k_prefix=self.k_prefix[i],
-                                v_prefix=self.v_prefix[i])
+            fp8 = self.k_prefix_scale is not None
+            return StaticKVSlot(
+                self, self.k[i], self.v[i], k_prefix=self.k_prefix[i],
+                v_prefix=self.v_prefix[i],
+                k_prefix_scale=self.k_prefix_scale[i] if fp8 else None,
+                v_prefix_scale=self.v_prefix_scale[i] if fp8 else None)
         return StaticKVSlot(self, self.k[i], self.v[i])
 
     def advance(self, n: int, rows: Optional[int] = None) -> None:
@@ -480,7 +515,9 @@ class MultiHeadAttention(nn.Module):
                 packed, slot.k_prefix, slot.v_prefix, own.prefix_lens,
                 slot.k, slot.v, own.lens, own.group, scale=self.scale,
                 max_prefix_len=slot.k_prefix.shape[2] if fixed
-                else max(own.prefix_max_len, 1))
+                else max(own.prefix_max_len, 1),
+                k_prefix_scale=slot.k_prefix_scale,
+                v_prefix_scale=slot.v_prefix_scale)
         return decode_attention(packed, slot.k, slot.v, slot.owner.lens,
                                 scale=self.scale,
                                 max_seq_len=slot.owner.max_seq_len
@@ -511,8 +548,16 @@ class MultiHeadAttention(nn.Module):
             assert prefill and S <= slot.k_prefix.shape[2], \
                 "shared-prompt prefill takes the P prompt rows, at most " \
                 f"{slot.k_prefix.shape[2]} tokens"
-            slot.k_prefix[:, :, :S].copy_(packed[:, :, :, 1].transpose(1, 2))
-            slot.v_prefix[:, :, :S].copy_(packed[:, :, :, 2].transpose(1, 2))
+            if slot.k_prefix_scale is not None:
+                # an fp8 prefix: the quantising store of the fp8 cache, over
+                # the P prompt rows
+                kv_cache_store_fp8(packed, slot.k_prefix, slot.v_prefix,
+                                   slot.k_prefix_scale, slot.v_prefix_scale)
+            else:
+                slot.k_prefix[:, :, :S].copy_(
+                    packed[:, :, :, 1].transpose(1, 2))
+                slot.v_prefix[:, :, :S].copy_(
+                    packed[:, :, :, 2].transpose(1, 2))
             if S == 1:  # softmax over one token: the output is its V
                 o = packed[:, :, :, 2].reshape(B, S, -1)
                 return self.out_proj(o), slot

@@ -275,6 +275,24 @@ def dequantize_kv_rows(codes: torch.Tensor, scale: torch.Tensor
     return codes.float() * scale.float()[..., None]
 
 
+def decode_attention_shared_fp8(qkv: torch.Tensor, k_prefix: torch.Tensor,
+                                v_prefix: torch.Tensor,
+                                k_prefix_scale: torch.Tensor,
+                                v_prefix_scale: torch.Tensor,
+                                prefix_lens: torch.Tensor,
+                                k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                seq_lens: torch.Tensor, group: int,
+                                scale: Optional[float] = None) -> torch.Tensor:
+    """decode_attention_shared over an fp8 prefix: k_prefix/v_prefix
+    [P, h, Lcap, D] float8_e4m3fn codes with one fp32 scale per stored row
+    ([P, h, Lcap], quantize_kv_rows). The prefix is dequantised to fp32; the
+    rows' own caches are not quantised and get the same in-place append."""
+    return decode_attention_shared(
+        qkv, dequantize_kv_rows(k_prefix, k_prefix_scale),
+        dequantize_kv_rows(v_prefix, v_prefix_scale), prefix_lens, k_cache,
+        v_cache, seq_lens, group, scale)
+
+
 def quantize_weight_rows(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-output-row fp8 quantisation of a linear's weight: w [N, K] ->
     (codes [N, K] float8_e4m3fn, scale [N] fp32), the arithmetic of

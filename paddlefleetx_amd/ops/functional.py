@@ -618,7 +618,8 @@ def decode_attention_shared(qkv, k_prefix, v_prefix, prefix_lens,
                             k_cache, v_cache, seq_lens, group: int,
                             scale: Optional[float] = None,
                             max_prefix_len: Optional[int] = None,
-                            num_splits: Optional[int] = None):
+                            num_splits: Optional[int] = None,
+                            k_prefix_scale=None, v_prefix_scale=None):
     """decode_attention for G = group samples of each prompt, the prompt's
     K/V stored and read ONCE per prompt (inference only).
 
@@ -640,6 +641,12 @@ def decode_attention_shared(qkv, k_prefix, v_prefix, prefix_lens,
     over the shared prefix, the decode_attention walk over the row's own
     tokens, one merge; an error if the extension is missing); everything
     else runs the fp32 reference twin with the same in-place semantics.
+
+    float8_e4m3fn k_prefix/v_prefix select the fp8 prefix mode and need
+    k_prefix_scale/v_prefix_scale (fp32 [P, h, Lcap], one scale per stored
+    row: what kv_cache_store_fp8 writes for the P prompt rows). Only the
+    prefix is fp8: k_cache/v_cache stay bf16 and the append is the same
+    (csrc/decode_attention_shared_fp8.hip). Same dispatch rule.
     """
     assert not (torch.is_grad_enabled() and (
         qkv.requires_grad or k_cache.requires_grad or v_cache.requires_grad
@@ -647,12 +654,32 @@ def decode_attention_shared(qkv, k_prefix, v_prefix, prefix_lens,
         "decode_attention_shared is inference-only (no autograd)"
     D = qkv.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    fp8 = k_prefix.dtype == torch.float8_e4m3fn
+    if fp8:
+        assert v_prefix.dtype == torch.float8_e4m3fn, \
+            "decode_attention_shared: k_prefix is fp8, v_prefix is not"
+        assert k_prefix_scale is not None and v_prefix_scale is not None, \
+            "decode_attention_shared: an fp8 prefix needs k_prefix_scale " \
+            "and v_prefix_scale"
+    else:
+        assert k_prefix_scale is None and v_prefix_scale is None, \
+            "decode_attention_shared: k_prefix_scale/v_prefix_scale go " \
+            "with an fp8 prefix only"
     if use_hip(qkv) and qkv.dtype == torch.bfloat16 and D in (64, 128):
         mpl = int(max_prefix_len) if max_prefix_len is not None \
             else k_prefix.shape[2]
+        if fp8:
+            return hip_ext().decode_attn_shared_fp8(
+                qkv, k_prefix, v_prefix, k_prefix_scale, v_prefix_scale,
+                prefix_lens, k_cache, v_cache, seq_lens, int(group),
+                float(scale), mpl, int(num_splits or 0))
         return hip_ext().decode_attn_shared(
             qkv, k_prefix, v_prefix, prefix_lens, k_cache, v_cache, seq_lens,
             int(group), float(scale), mpl, int(num_splits or 0))
+    if fp8:
+        return ref.decode_attention_shared_fp8(
+            qkv, k_prefix, v_prefix, k_prefix_scale, v_prefix_scale,
+            prefix_lens, k_cache, v_cache, seq_lens, int(group), scale)
     return ref.decode_attention_shared(qkv, k_prefix, v_prefix, prefix_lens,
                                        k_cache, v_cache, seq_lens, int(group),
                                        scale)

@@ -29,6 +29,7 @@ hip_sources = [
     for s in ("bindings.cpp", "layernorm.hip", "elementwise.hip",
               "softmax.hip", "attention.hip", "decode_attention.hip",
               "decode_attention_fp8.hip", "decode_attention_shared.hip",
+              "decode_attention_shared_fp8.hip",
               "decode_linear.hip",
               "decode_linear_fp8.hip", "decode_linear_mxfp4.hip",
               "decode_linear_wide.hip", "decode_linear_wide_mxfp4.hip",
