@@ -41,27 +41,11 @@
 // the chunk's positions 32 at a time, each with its own (m, l, acc) and its
 // own image: no workgroup barrier in the walk. At the end every wave leaves
 // its state in its own region and the workgroup merges them in wave order.
-#include "decode_attention_kernel.h"
-
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
+#include "decode_attention_shared_common.h"
 
 namespace {
 
-constexpr int PNW = 4;         // waves per prefix workgroup
-constexpr int PSTEP = 32;      // positions per wave step (two score tiles)
 constexpr int VT_STRIDE = 40;  // shorts per row of the transposed V image
-constexpr int COLS = 16;       // samples per column group (MFMA N)
-
-DEV_INLINE mfma_bf16x8 frag(const short8v& v) {
-  return __builtin_bit_cast(mfma_bf16x8, v);
-}
-
-// position (inside a 32-position step) of column c of the permuted order
-DEV_INLINE int perm_pos(int c) {
-  const int gg = c >> 3, jj = c & 7;
-  return (jj < 4) ? gg * 4 + jj : 16 + gg * 4 + (jj - 4);
-}
 
 // grid (P*h*ncg, chunks), 256 threads.
 // ws: fp32 [B*h, ws_slots, D+4]; chunk ck goes to slot 1 + ck.
@@ -89,12 +73,8 @@ __global__ __launch_bounds__(PNW * WAVE) void decode_prefix_kernel(
   const int wid = tid / WAVE;
   const int r = lane & 15, g = lane >> 4;
 
-  // a bad length gives wrong numbers, never an out-of-bounds address
-  const int Lp = min(max(prefix_lens[p], 0), Lcap);
-  // positions [start, end) of this chunk; the last one runs to Lp so an
-  // under-estimated max_prefix_len cannot drop positions
-  const int start = min(ck * chunk, Lp);
-  const int end = (ck == nck - 1) ? Lp : min((ck + 1) * chunk, Lp);
+  int start, end;  // positions of this chunk
+  chunk_bounds(prefix_lens[p], Lcap, chunk, ck, nck, start, end);
 
   const short8v zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   // Q^T: column = sample; columns >= G are zero and never stored
@@ -223,87 +203,13 @@ __global__ __launch_bounds__(PNW * WAVE) void decode_prefix_kernel(
     }
   }
 
-  // this wave's state -> its own region: [sample][acc[D], m, l, pad]
-  l += __shfl_xor(l, 16, WAVE);
-  l += __shfl_xor(l, 32, WAVE);
-  __builtin_amdgcn_wave_barrier();
-  {
-    float* sw = reinterpret_cast<float*>(vt) + r * SROW;
-#pragma unroll
-    for (int db = 0; db < DB; ++db)
-      *reinterpret_cast<mfma_f32x4*>(sw + db * 16 + g * 4) = acc[db];
-    if (g == 0) { sw[D] = m; sw[D + 1] = l; }
-  }
+  // this wave's state -> its own region, over its V image
+  store_wave_state<D>(reinterpret_cast<float*>(vt), r, g, acc, m, l);
   __syncthreads();
 
-  // thread (sample c, channels d0 .. d0 + D/16) merges the waves in wave order
-  constexpr int ND = D / 16;
-  const int c = tid & 15;
-  const int d0 = (tid >> 4) * ND;
-  const float* s0 = reinterpret_cast<const float*>(s_vt[0]) + c * SROW;
-  constexpr int WSTRIDE = D * VT_STRIDE / 2;  // floats between wave regions
-  float M = -INFINITY;
-#pragma unroll
-  for (int w = 0; w < PNW; ++w) M = fmaxf(M, s0[w * WSTRIDE + D]);
-  const float Ms = (M == -INFINITY) ? 0.f : M;
-  float Lsum = 0.f;
-  float o[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) o[i] = 0.f;
-#pragma unroll
-  for (int w = 0; w < PNW; ++w) {
-    const float* sw = s0 + w * WSTRIDE;
-    const float m_w = sw[D];
-    const float wt = (m_w == -INFINITY) ? 0.f : __expf(m_w - Ms);
-    Lsum = fmaf(wt, sw[D + 1], Lsum);
-#pragma unroll
-    for (int i = 0; i < ND; i += 4) {
-      const float4v a = *reinterpret_cast<const float4v*>(sw + d0 + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[i + e] = fmaf(wt, a[e], o[i + e]);
-    }
-  }
-  const int sc = cg * COLS + c;
-  if (sc < G) {
-    float* w = ws + (((size_t)(p * G + sc) * h + head) * ws_slots + 1 + ck) *
-                        (D + 4);
-#pragma unroll
-    for (int i = 0; i < ND; i += 4) {
-      const float4v a = {o[i], o[i + 1], o[i + 2], o[i + 3]};
-      *reinterpret_cast<float4v*>(w + d0 + i) = a;
-    }
-    if (d0 == 0) { w[D] = M; w[D + 1] = Lsum; }
-  }
-}
-
-template <int D>
-void launch_shared(torch::Tensor& qkv, torch::Tensor& kp, torch::Tensor& vp,
-                   torch::Tensor& plens, torch::Tensor& kc, torch::Tensor& vc,
-                   torch::Tensor& lens, torch::Tensor& out, long P, long G,
-                   long h, long Lcap, long Scap, long max_prefix_len,
-                   int chunks, float scale) {
-  auto stream = at::hip::getCurrentHIPStream();
-  const long B = P * G;
-  const int slots = chunks + 1;
-  const int ncg = (int)((G + COLS - 1) / COLS);
-  auto ws = torch::empty({B * h, (long)slots, (long)D + 4},
-                         qkv.options().dtype(torch::kFloat));
-  float* wsp = ws.data_ptr<float>();
-  const int chunk = (int)((max_prefix_len + chunks - 1) / chunks);
-  hipLaunchKernelGGL(decode_prefix_kernel<D>, dim3(P * h * ncg, chunks),
-                     dim3(PNW * WAVE), 0, stream, (const short*)qkv.data_ptr(),
-                     (const short*)kp.data_ptr(), (const short*)vp.data_ptr(),
-                     plens.data_ptr<int>(), wsp, (int)h, (int)G, ncg,
-                     (int)Lcap, chunk, slots, scale);
-  hipLaunchKernelGGL((decode_attn_kernel<D, true>), dim3(B * h, 1),
-                     dim3(BLOCK), 0, stream, (const short*)qkv.data_ptr(),
-                     (short*)kc.data_ptr(), (short*)vc.data_ptr(),
-                     lens.data_ptr<int>(), (short*)out.data_ptr(), wsp, (int)h,
-                     (int)Scap, (int)Scap, scale,
-                     (const int*)plens.data_ptr<int>(), (int)G, (int)Lcap,
-                     slots);
-  hipLaunchKernelGGL(decode_merge_kernel<D>, dim3(B * h), dim3(D), 0, stream,
-                     (const float*)wsp, (short*)out.data_ptr(), slots);
+  // the regions are the images: D * VT_STRIDE / 2 floats apart
+  merge_waves<D, D * VT_STRIDE / 2>(reinterpret_cast<const float*>(s_vt[0]),
+                                    ws, tid, cg, p, head, ck, h, G, ws_slots);
 }
 
 }  // namespace
@@ -315,75 +221,24 @@ torch::Tensor decode_attn_shared(torch::Tensor qkv, torch::Tensor k_prefix,
                                  torch::Tensor seq_lens, long group,
                                  double scale, long max_prefix_len,
                                  long num_splits) {
-  const torch::Tensor* all[] = {&qkv,     &k_prefix, &v_prefix, &prefix_lens,
-                                &k_cache, &v_cache,  &seq_lens};
-  for (const torch::Tensor* t : all) {
-    TORCH_CHECK(t->is_cuda(),
-                "decode_attn_shared: all tensors must be on the GPU");
-    TORCH_CHECK(t->device() == qkv.device(),
-                "decode_attn_shared: tensors must share one device");
-    TORCH_CHECK(t->is_contiguous(),
-                "decode_attn_shared: tensors must be contiguous");
-  }
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 &&
-                  k_prefix.scalar_type() == torch::kBFloat16 &&
-                  v_prefix.scalar_type() == torch::kBFloat16 &&
-                  k_cache.scalar_type() == torch::kBFloat16 &&
-                  v_cache.scalar_type() == torch::kBFloat16,
-              "decode_attn_shared: qkv, prefix and caches must be bf16");
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(1) == 1 && qkv.size(3) == 3,
-              "decode_attn_shared: qkv must be [B, 1, h, 3, D]");
-  const long B = qkv.size(0), h = qkv.size(2), D = qkv.size(4);
-  TORCH_CHECK(D == 64 || D == 128,
-              "decode_attn_shared: head_dim must be 64 or 128");
-  TORCH_CHECK(group >= 1 && B >= 1 && B % group == 0,
-              "decode_attn_shared: group must be >= 1 and divide B");
-  TORCH_CHECK(k_prefix.dim() == 4 && k_prefix.size(1) == h &&
-                  k_prefix.size(3) == D,
-              "decode_attn_shared: k_prefix must be [P, h, Lcap, D]");
-  TORCH_CHECK(v_prefix.sizes() == k_prefix.sizes(),
-              "decode_attn_shared: v_prefix shape must equal k_prefix shape");
-  const long P = k_prefix.size(0), Lcap = k_prefix.size(2);
-  TORCH_CHECK(P * group == B,
-              "decode_attn_shared: P * group must equal B (rows are grouped "
-              "by prompt)");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == B &&
-                  k_cache.size(1) == h && k_cache.size(3) == D,
-              "decode_attn_shared: k_cache must be [B, h, Scap, D]");
-  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(),
-              "decode_attn_shared: v_cache shape must equal k_cache shape");
-  const long Scap = k_cache.size(2);
-  TORCH_CHECK(Scap >= 1 && Lcap >= 1 && h >= 1 &&
-                  B * h * Scap * D < (1L << 40) &&
-                  P * h * Lcap * D < (1L << 40) && B * h < (1L << 30),
-              "decode_attn_shared: bad cache extent");
-  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt && seq_lens.dim() == 1 &&
-                  seq_lens.size(0) == B,
-              "decode_attn_shared: seq_lens must be int32 [B]");
-  TORCH_CHECK(prefix_lens.scalar_type() == torch::kInt &&
-                  prefix_lens.dim() == 1 && prefix_lens.size(0) == P,
-              "decode_attn_shared: prefix_lens must be int32 [P]");
-  TORCH_CHECK(max_prefix_len >= 1 && max_prefix_len <= Lcap,
-              "decode_attn_shared: max_prefix_len must be in [1, Lcap]");
-  TORCH_CHECK(num_splits >= 0 && num_splits <= MAX_SPLITS - 1,
-              "decode_attn_shared: num_splits must be 0 (auto) or 1..31 "
-              "prefix chunks");
-
-  int chunks = (int)num_splits;
-  if (chunks == 0) {
-    const int cus =
-        at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-    const long wgs = P * h * ((group + COLS - 1) / COLS);
-    chunks = std::min(choose_splits(wgs, max_prefix_len, cus), MAX_SPLITS - 1);
-  }
-  auto out = torch::empty({B, 1, h * D}, qkv.options());
-  if (D == 64)
-    launch_shared<64>(qkv, k_prefix, v_prefix, prefix_lens, k_cache, v_cache,
-                      seq_lens, out, P, group, h, Lcap, Scap, max_prefix_len,
-                      chunks, (float)scale);
-  else
-    launch_shared<128>(qkv, k_prefix, v_prefix, prefix_lens, k_cache, v_cache,
-                       seq_lens, out, P, group, h, Lcap, Scap, max_prefix_len,
-                       chunks, (float)scale);
-  return out;
+  const SharedDims s = check_decode_attn_shared(
+      "decode_attn_shared", qkv, k_prefix, v_prefix, prefix_lens, k_cache,
+      v_cache, seq_lens, group, max_prefix_len, num_splits, torch::kBFloat16);
+  auto run = [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    return launch_shared<D>(
+        qkv, prefix_lens, k_cache, v_cache, seq_lens, s, group, max_prefix_len,
+        num_splits, (float)scale,
+        [&](dim3 grid, hipStream_t stream, float* wsp, int ncg, int chunk,
+            int slots) {
+          hipLaunchKernelGGL(
+              decode_prefix_kernel<D>, grid, dim3(PNW * WAVE), 0, stream,
+              (const short*)qkv.data_ptr(), (const short*)k_prefix.data_ptr(),
+              (const short*)v_prefix.data_ptr(), prefix_lens.data_ptr<int>(),
+              wsp, (int)s.h, (int)group, ncg, (int)s.Lcap, chunk, slots,
+              (float)scale);
+        });
+  };
+  return s.D == 64 ? run(std::integral_constant<int, 64>{})
+                   : run(std::integral_constant<int, 128>{});
 }

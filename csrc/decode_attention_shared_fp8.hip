@@ -50,21 +50,12 @@
 // scales are zero by select and their scores -inf by select, so a NaN code or
 // scale past the end never reaches an MFMA. Sample columns >= G carry a zero
 // Q and are never stored.
-#include "decode_attention_kernel.h"
-
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <cstdint>
+#include "decode_attention_shared_common.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) int int4v;
 typedef __attribute__((ext_vector_type(2))) int int2v;
-
-constexpr int PNW = 4;     // waves per prefix workgroup
-constexpr int PSTEP = 32;  // positions per wave step (two score tiles)
-constexpr int COLS = 16;   // samples per column group (MFMA N)
 
 // Byte image Vt8: row d (a channel) holds the step's 32 codes in the permuted
 // order and starts at d*VT8_STRIDE + (d >> 4)*VT8_SKEW.
@@ -83,10 +74,6 @@ constexpr int COLS = 16;   // samples per column group (MFMA N)
 // D = 64 (8 rows per lane) two cb share a block and writes stay 2-way.
 constexpr int VT8_STRIDE = 40;
 constexpr int VT8_SKEW = 32;
-
-DEV_INLINE mfma_bf16x8 frag(const short8v& v) {
-  return __builtin_bit_cast(mfma_bf16x8, v);
-}
 
 // 8 e4m3 codes (two words) -> 8 bf16, exact: the high halves of the fp32
 // pairs v_cvt_pk_f32_fp8 gives, packed by v_perm_b32 (4 VALU ops per 4 codes)
@@ -154,12 +141,8 @@ __global__ __launch_bounds__(PNW * WAVE) void decode_prefix_fp8_kernel(
   const int wid = tid / WAVE;
   const int r = lane & 15, g = lane >> 4;
 
-  // a bad length gives wrong numbers, never an out-of-bounds address
-  const int Lp = min(max(prefix_lens[p], 0), Lcap);
-  // positions [start, end) of this chunk; the last one runs to Lp so an
-  // under-estimated max_prefix_len cannot drop positions
-  const int start = min(ck * chunk, Lp);
-  const int end = (ck == nck - 1) ? Lp : min((ck + 1) * chunk, Lp);
+  int start, end;  // positions of this chunk
+  chunk_bounds(prefix_lens[p], Lcap, chunk, ck, nck, start, end);
 
   const short8v zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   // Q^T: column = sample; columns >= G are zero and never stored. Fragment
@@ -184,7 +167,7 @@ __global__ __launch_bounds__(PNW * WAVE) void decode_prefix_fp8_kernel(
   // V image items of this lane: columns 4*vq .. + 4 of the permuted order,
   // which are positions va .. va + 4 of the step, channels vcb*(D/8) .. + D/8
   const int vcb = lane & 7, vq = lane >> 3;
-  const int va = (vq & 1) * 16 + (vq >> 1) * 4;
+  const int va = perm_pos(4 * vq);
   const unsigned char* vbase =
       v_prefix + (size_t)ph * Lcap * D + vcb * (D / 8);
   // lanes 0-31: K scale, lanes 32-63: V scale of position lane & 31
@@ -329,95 +312,12 @@ __global__ __launch_bounds__(PNW * WAVE) void decode_prefix_fp8_kernel(
     }
   }
 
-  // this wave's state -> its own region: [sample][acc[D], m, l, pad]
-  l += __shfl_xor(l, 16, WAVE);
-  l += __shfl_xor(l, 32, WAVE);
-  __builtin_amdgcn_wave_barrier();
-  {
-    float* sw = reinterpret_cast<float*>(vt) + r * SROW;
-#pragma unroll
-    for (int db = 0; db < DB; ++db)
-      *reinterpret_cast<mfma_f32x4*>(sw + db * 16 + g * 4) = acc[db];
-    if (g == 0) { sw[D] = m; sw[D + 1] = l; }
-  }
+  // this wave's state -> its own region, over its V image
+  store_wave_state<D>(reinterpret_cast<float*>(vt), r, g, acc, m, l);
   __syncthreads();
 
-  // thread (sample c, channels d0 .. d0 + D/16) merges the waves in wave order
-  constexpr int ND = D / 16;
-  const int c = tid & 15;
-  const int d0 = (tid >> 4) * ND;
-  const float* s0 = reinterpret_cast<const float*>(s_vt[0]) + c * SROW;
-  constexpr int WSTRIDE = REGION / 4;  // floats between wave regions
-  float M = -INFINITY;
-#pragma unroll
-  for (int w = 0; w < PNW; ++w) M = fmaxf(M, s0[w * WSTRIDE + D]);
-  const float Ms = (M == -INFINITY) ? 0.f : M;
-  float Lsum = 0.f;
-  float o[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) o[i] = 0.f;
-#pragma unroll
-  for (int w = 0; w < PNW; ++w) {
-    const float* sw = s0 + w * WSTRIDE;
-    const float m_w = sw[D];
-    const float wt = (m_w == -INFINITY) ? 0.f : __expf(m_w - Ms);
-    Lsum = fmaf(wt, sw[D + 1], Lsum);
-#pragma unroll
-    for (int i = 0; i < ND; i += 4) {
-      const float4v a = *reinterpret_cast<const float4v*>(sw + d0 + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[i + e] = fmaf(wt, a[e], o[i + e]);
-    }
-  }
-  const int sc_out = cg * COLS + c;
-  if (sc_out < G) {
-    float* w = ws + (((size_t)(p * G + sc_out) * h + head) * ws_slots + 1 +
-                     ck) * (D + 4);
-#pragma unroll
-    for (int i = 0; i < ND; i += 4) {
-      const float4v a = {o[i], o[i + 1], o[i + 2], o[i + 3]};
-      *reinterpret_cast<float4v*>(w + d0 + i) = a;
-    }
-    if (d0 == 0) { w[D] = M; w[D + 1] = Lsum; }
-  }
-}
-
-template <int D>
-void launch_shared_fp8(torch::Tensor& qkv, torch::Tensor& kp,
-                       torch::Tensor& vp, torch::Tensor& kps,
-                       torch::Tensor& vps, torch::Tensor& plens,
-                       torch::Tensor& kc, torch::Tensor& vc,
-                       torch::Tensor& lens, torch::Tensor& out, long P, long G,
-                       long h, long Lcap, long Scap, long max_prefix_len,
-                       int chunks, float scale) {
-  auto stream = at::hip::getCurrentHIPStream();
-  const long B = P * G;
-  const int slots = chunks + 1;
-  const int ncg = (int)((G + COLS - 1) / COLS);
-  auto ws = torch::empty({B * h, (long)slots, (long)D + 4},
-                         qkv.options().dtype(torch::kFloat));
-  float* wsp = ws.data_ptr<float>();
-  const int chunk = (int)((max_prefix_len + chunks - 1) / chunks);
-  hipLaunchKernelGGL(decode_prefix_fp8_kernel<D>, dim3(P * h * ncg, chunks),
-                     dim3(PNW * WAVE), 0, stream, (const short*)qkv.data_ptr(),
-                     (const unsigned char*)kp.data_ptr(),
-                     (const unsigned char*)vp.data_ptr(),
-                     kps.data_ptr<float>(), vps.data_ptr<float>(),
-                     plens.data_ptr<int>(), wsp, (int)h, (int)G, ncg,
-                     (int)Lcap, chunk, slots, scale);
-  hipLaunchKernelGGL((decode_attn_kernel<D, true>), dim3(B * h, 1),
-                     dim3(BLOCK), 0, stream, (const short*)qkv.data_ptr(),
-                     (short*)kc.data_ptr(), (short*)vc.data_ptr(),
-                     lens.data_ptr<int>(), (short*)out.data_ptr(), wsp, (int)h,
-                     (int)Scap, (int)Scap, scale,
-                     (const int*)plens.data_ptr<int>(), (int)G, (int)Lcap,
-                     slots);
-  hipLaunchKernelGGL(decode_merge_kernel<D>, dim3(B * h), dim3(D), 0, stream,
-                     (const float*)wsp, (short*)out.data_ptr(), slots);
-}
-
-bool aligned16(const torch::Tensor& t) {
-  return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
+  merge_waves<D, REGION / 4>(reinterpret_cast<const float*>(s_vt[0]), ws, tid,
+                             cg, p, head, ck, h, G, ws_slots);
 }
 
 }  // namespace
@@ -428,21 +328,10 @@ torch::Tensor decode_attn_shared_fp8(
     torch::Tensor prefix_lens, torch::Tensor k_cache, torch::Tensor v_cache,
     torch::Tensor seq_lens, long group, double scale, long max_prefix_len,
     long num_splits) {
-  const torch::Tensor* all[] = {&qkv,         &k_prefix,       &v_prefix,
-                                &k_prefix_scale, &v_prefix_scale, &prefix_lens,
-                                &k_cache,     &v_cache,        &seq_lens};
-  for (const torch::Tensor* t : all) {
-    TORCH_CHECK(t->is_cuda(),
-                "decode_attn_shared_fp8: all tensors must be on the GPU");
-    TORCH_CHECK(t->device() == qkv.device(),
-                "decode_attn_shared_fp8: tensors must share one device");
-    TORCH_CHECK(t->is_contiguous(),
-                "decode_attn_shared_fp8: tensors must be contiguous");
-  }
-  TORCH_CHECK(k_prefix.scalar_type() == torch::kFloat8_e4m3fn &&
-                  v_prefix.scalar_type() == torch::kFloat8_e4m3fn,
-              "decode_attn_shared_fp8: k_prefix and v_prefix must be "
-              "float8_e4m3fn");
+  const SharedDims s = check_decode_attn_shared(
+      "decode_attn_shared_fp8", qkv, k_prefix, v_prefix, prefix_lens, k_cache,
+      v_cache, seq_lens, group, max_prefix_len, num_splits,
+      torch::kFloat8_e4m3fn, {&k_prefix_scale, &v_prefix_scale});
   TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 &&
                   k_cache.scalar_type() == torch::kBFloat16 &&
                   v_cache.scalar_type() == torch::kBFloat16,
@@ -451,71 +340,34 @@ torch::Tensor decode_attn_shared_fp8(
   TORCH_CHECK(k_prefix_scale.scalar_type() == torch::kFloat &&
                   v_prefix_scale.scalar_type() == torch::kFloat,
               "decode_attn_shared_fp8: prefix scales must be fp32");
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(1) == 1 && qkv.size(3) == 3,
-              "decode_attn_shared_fp8: qkv must be [B, 1, h, 3, D]");
-  const long B = qkv.size(0), h = qkv.size(2), D = qkv.size(4);
-  TORCH_CHECK(D == 64 || D == 128,
-              "decode_attn_shared_fp8: head_dim must be 64 or 128");
-  TORCH_CHECK(group >= 1 && B >= 1 && B % group == 0,
-              "decode_attn_shared_fp8: group must be >= 1 and divide B");
-  TORCH_CHECK(k_prefix.dim() == 4 && k_prefix.size(1) == h &&
-                  k_prefix.size(3) == D,
-              "decode_attn_shared_fp8: k_prefix must be [P, h, Lcap, D]");
-  TORCH_CHECK(v_prefix.sizes() == k_prefix.sizes(),
-              "decode_attn_shared_fp8: v_prefix shape must equal k_prefix "
-              "shape");
-  const long P = k_prefix.size(0), Lcap = k_prefix.size(2);
-  TORCH_CHECK(k_prefix_scale.dim() == 3 && k_prefix_scale.size(0) == P &&
-                  k_prefix_scale.size(1) == h &&
-                  k_prefix_scale.size(2) == Lcap &&
+  TORCH_CHECK(k_prefix_scale.dim() == 3 && k_prefix_scale.size(0) == s.P &&
+                  k_prefix_scale.size(1) == s.h &&
+                  k_prefix_scale.size(2) == s.Lcap &&
                   v_prefix_scale.sizes() == k_prefix_scale.sizes(),
               "decode_attn_shared_fp8: prefix scales must be [P, h, Lcap]");
-  TORCH_CHECK(P * group == B,
-              "decode_attn_shared_fp8: P * group must equal B (rows are "
-              "grouped by prompt)");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == B &&
-                  k_cache.size(1) == h && k_cache.size(3) == D,
-              "decode_attn_shared_fp8: k_cache must be [B, h, Scap, D]");
-  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(),
-              "decode_attn_shared_fp8: v_cache shape must equal k_cache shape");
-  const long Scap = k_cache.size(2);
-  TORCH_CHECK(Scap >= 1 && Lcap >= 1 && h >= 1 &&
-                  B * h * Scap * D < (1L << 40) &&
-                  P * h * Lcap * D < (1L << 40) && B * h < (1L << 30),
-              "decode_attn_shared_fp8: bad cache extent");
-  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt && seq_lens.dim() == 1 &&
-                  seq_lens.size(0) == B,
-              "decode_attn_shared_fp8: seq_lens must be int32 [B]");
-  TORCH_CHECK(prefix_lens.scalar_type() == torch::kInt &&
-                  prefix_lens.dim() == 1 && prefix_lens.size(0) == P,
-              "decode_attn_shared_fp8: prefix_lens must be int32 [P]");
-  TORCH_CHECK(max_prefix_len >= 1 && max_prefix_len <= Lcap,
-              "decode_attn_shared_fp8: max_prefix_len must be in [1, Lcap]");
-  TORCH_CHECK(num_splits >= 0 && num_splits <= MAX_SPLITS - 1,
-              "decode_attn_shared_fp8: num_splits must be 0 (auto) or 1..31 "
-              "prefix chunks");
   TORCH_CHECK(aligned16(qkv) && aligned16(k_prefix) && aligned16(v_prefix) &&
                   aligned16(k_cache) && aligned16(v_cache),
               "decode_attn_shared_fp8: qkv, prefix and caches must be 16-byte "
               "aligned");
-
-  int chunks = (int)num_splits;
-  if (chunks == 0) {
-    const int cus =
-        at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-    const long wgs = P * h * ((group + COLS - 1) / COLS);
-    chunks = std::min(choose_splits(wgs, max_prefix_len, cus), MAX_SPLITS - 1);
-  }
-  auto out = torch::empty({B, 1, h * D}, qkv.options());
-  if (D == 64)
-    launch_shared_fp8<64>(qkv, k_prefix, v_prefix, k_prefix_scale,
-                          v_prefix_scale, prefix_lens, k_cache, v_cache,
-                          seq_lens, out, P, group, h, Lcap, Scap,
-                          max_prefix_len, chunks, (float)scale);
-  else
-    launch_shared_fp8<128>(qkv, k_prefix, v_prefix, k_prefix_scale,
-                           v_prefix_scale, prefix_lens, k_cache, v_cache,
-                           seq_lens, out, P, group, h, Lcap, Scap,
-                           max_prefix_len, chunks, (float)scale);
-  return out;
+  auto run = [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    return launch_shared<D>(
+        qkv, prefix_lens, k_cache, v_cache, seq_lens, s, group, max_prefix_len,
+        num_splits, (float)scale,
+        [&](dim3 grid, hipStream_t stream, float* wsp, int ncg, int chunk,
+            int slots) {
+          hipLaunchKernelGGL(
+              decode_prefix_fp8_kernel<D>, grid, dim3(PNW * WAVE), 0, stream,
+              (const short*)qkv.data_ptr(),
+              (const unsigned char*)k_prefix.data_ptr(),
+              (const unsigned char*)v_prefix.data_ptr(),
+              k_prefix_scale.data_ptr<float>(),
+              v_prefix_scale.data_ptr<float>(), prefix_lens.data_ptr<int>(),
+              wsp, (int)s.h, (int)group, ncg, (int)s.Lcap, chunk, slots,
+              (float)scale);
+        });
+  };
+  return s.D == 64 ? run(std::integral_constant<int, 64>{})
+                   : run(std::integral_constant<int, 128>{});
 }
+

@@ -197,24 +197,42 @@ def test_nan_query_stays_in_its_row():
     (dict(slcap=15), "scales must be \\[P, h, Lcap\\]"),
     (dict(cdtype=F8), "k_cache and v_cache must be bf16"),
     (dict(group=0), "group"), (dict(mpl=17), "max_prefix_len"),
+    # the checks shared with decode_attn_shared, through this entry point
+    (dict(d=32), "head_dim"), (dict(P=2), "P \\* group"),
+    (dict(group=4), "group"), (dict(mpl=0), "max_prefix_len"),
+    (dict(splits=32), "num_splits"),
+    (dict(lens_long=True), "seq_lens must be int32"),
+    (dict(plens_long=True), "prefix_lens must be int32"),
+    (dict(strided=True), "contiguous"), (dict(cpu=True), "on the GPU"),
+    (dict(Scap_v=9), "v_cache shape"),
+    (dict(qkv_offset=1), "16-byte aligned"),
 ])
 def test_refusals(change, match):
     """Host checks fire before any launch and name the op."""
     dev = torch.device("cuda:0")
     c = dict(pdtype=F8, sdtype=torch.float32, slcap=16, cdtype=BF, group=2,
-             mpl=16)
+             mpl=16, d=64, P=3, splits=0, lens_long=False, plens_long=False,
+             strided=False, cpu=False, Scap_v=8, qkv_offset=0)
     c.update(change)
-    B, h, d, P = 6, 2, 64, 3
-    qkv = torch.zeros(B, 1, h, 3, d, device=dev, dtype=BF)
+    B, h, d, P = 6, 2, c["d"], c["P"]
+    # a contiguous view qkv_offset bf16 elements into a larger buffer
+    n = B * h * 3 * d
+    qkv = torch.zeros(n + 8, device=dev, dtype=BF)[
+        c["qkv_offset"]:c["qkv_offset"] + n].view(B, 1, h, 3, d)
     kp = torch.zeros(P, h, 16, d, device=dev).to(c["pdtype"])
+    if c["strided"]:
+        kp = kp.transpose(1, 2).contiguous().transpose(1, 2)
     sc = torch.ones(P, h, c["slcap"], device=dev, dtype=c["sdtype"])
     kc = torch.zeros(B, h, 8, d, device=dev).to(c["cdtype"])
+    vc = torch.zeros(B, h, c["Scap_v"], d, device=dev).to(c["cdtype"])
     pl = torch.zeros(P, dtype=torch.int32, device=dev)
     lens = torch.zeros(B, dtype=torch.int32, device=dev)
     with pytest.raises(RuntimeError, match="decode_attn_shared_fp8.*" + match):
         hip_ext().decode_attn_shared_fp8(
-            qkv, kp, kp.clone(), sc, sc.clone(), pl, kc, kc.clone(), lens,
-            c["group"], 0.125, c["mpl"], 0)
+            qkv, kp, kp.clone(), sc, sc.clone(),
+            pl.long() if c["plens_long"] else pl, kc, vc,
+            lens.long() if c["lens_long"] else lens.cpu() if c["cpu"]
+            else lens, c["group"], 0.125, c["mpl"], c["splits"])
 
 
 GPT = dict(vocab_size=512, hidden_size=256, num_layers=2,
